@@ -10,11 +10,19 @@ clock).  Rank 0 prints ONE JSON line.
 
 Inputs: synthetic but valid group elements -- all (P_i, Q_j), i,j < 1024, from the
 committed fixture tests/golden/a_chain1024.vec (P_i=(i+1)P0, Q_j=(j+1)Q0, SURVEY.md 8d);
-2^20 distinct pairs.  Before timing, the diagonal of one result batch is compared with the
-reference's own outputs stored in the fixture (bit-exact) -- a wrong kernel cannot post a
-number.
+2^20 distinct pairs, the same on every run with the same arguments.
+
+A plain run sets up, warms up, times the K steps and prints the line (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step` = wall-clock milliseconds of one timed step).
+--full adds everything else: before timing, the diagonal of one result batch is compared with
+the reference's own outputs stored in the fixture (bit-exact) -- a wrong kernel cannot post a
+number -- and after it the host-buffer path, the live multiply-add probe, the CPU baseline and
+the card's clock / power during the timed steps.  --dump-outputs DIR writes what the last timed
+step computed (DIR/<name>.npy, float32; a fixed sample of rows where the output is larger than
+DUMP_BUDGET) so that two builds can be compared output for output.
 """
 import argparse
+import contextlib
 import json
 import os
 import struct
@@ -57,6 +65,26 @@ HBM_PEAK_GBS = 8000.0      # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 # dual-issue / packed figure; the 32 x 32 + 64-bit multiply-add runs at half of it).  A constant, so that `frac` is
 # reproducible; the live probe of the same pipe is reported beside it as peak_measured.
 MAC_PEAK = 256 * 4 * 16 * 2.4e9
+
+
+DUMP_BUDGET = 48 << 20     # bytes of float32 values of all dumped outputs together (plus 8 bytes of row index per sampled row)
+
+
+def dump_outputs(out_dir, outputs):
+    """--dump-outputs: outputs = {name: 2-D uint8 tensor of records (element_to_bytes / Z_r bytes), one row per unit}.
+    Writes DIR/<name>.npy (the bytes as float32 values, exact) and, where the rows had to be sampled to stay within
+    DUMP_BUDGET, DIR/<name>_rows.npy (float64 row indices of a fixed seeded sample, the same on every run)."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in outputs.items():
+        n, width = t.shape[0], t.shape[1]
+        rows = max(1, DUMP_BUDGET // len(outputs) // (4 * width))
+        if n > rows:
+            idx = np.sort(np.random.default_rng(20260).choice(n, size=rows, replace=False))
+            vals = t[torch.from_numpy(idx).to(t.device)].cpu().numpy()
+            np.save(os.path.join(out_dir, name + "_rows.npy"), idx.astype(np.float64))
+        else:
+            vals = t.cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), vals.astype(np.float32))
 
 
 def load_vec(path):
@@ -327,7 +355,14 @@ def main():
     ap.add_argument("--no-host-path", action="store_true",
                     help="skip the pinned-host -> host timing of the host-buffer entry point (reported beside `value`, never as it)")
     ap.add_argument("--host-path", action="store_true", help=argparse.SUPPRESS)     # round-1 spelling: now the default
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: the pre-timing gate against the reference fixture, the host-buffer path, the live "
+                         "multiply-add probe (roofline.peak_measured), the CPU baseline and the clock / power sampler")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.workload in bench_group.GROUP_WORKLOADS:
         return bench_group.main(args, load_vec, ensure_built, MAC_PEAK)
     pname, fixture, k, dlog, desc = WORKLOADS[args.workload]
@@ -392,14 +427,16 @@ def main():
             dist.barrier()
             torch.cuda.synchronize()
 
-    for _ in range(max(1, args.warmup)):
-        step()
-    torch.cuda.synchronize()
-    # correctness gate against the reference's own outputs stored in the fixture, on EVERY rank and shard: unit u of this
-    # rank's shard is term t = first + u, which pairs P_a with Q_b, a = (t // D) % D, b = (t % D + rot) % D; wherever a == b
-    # the result must be the fixture's e(P_a, Q_a).  k > 1: the term-order check below (also on every rank).
+    # correctness gate against the reference's own outputs stored in the fixture, on EVERY rank and shard (--full; --sweep): unit
+    # u of this rank's shard is term t = first + u, which pairs P_a with Q_b, a = (t // D) % D, b = (t % D + rot) % D; wherever
+    # a == b the result must be the fixture's e(P_a, Q_a).  k > 1: the term-order check below (also on every rank).
+    gate_on = args.full or args.sweep
+    if gate_on:
+        for _ in range(max(1, args.warmup)):
+            step()
+        torch.cuda.synchronize()
     gated_units = 0
-    if pp is not None:
+    if gate_on and pp is not None:
         if rot == 0 and first == 0 and not np.array_equal(GT[0].cpu().numpy(), gt_ref[0]):     # unit 0 is e(P_0, Q_0)
             sys.exit("bench.py: pp_apply differs from the reference fixture -- refusing to time")
         chk = torch.empty(256, LT, dtype=torch.uint8, device="cuda")
@@ -409,13 +446,13 @@ def main():
         if not torch.equal(chk, GT[:256]):
             sys.exit("bench.py: pp_apply differs from element_pairing -- refusing to time")
         gated_units = 256
-    elif k == 1:
+    elif gate_on and k == 1:
         a_idx, b_idx = (t // D) % D, (t % D + rot) % D
         diag = torch.nonzero(a_idx == b_idx).flatten()[:D]
         if len(diag) and not np.array_equal(GT[diag].cpu().numpy(), gt_ref[a_idx[diag].cpu().numpy()]):
             sys.exit("bench.py: GPU results of rank %d differ from the reference fixture -- refusing to time" % rank)
         gated_units = int(len(diag))
-    if k > 1:
+    if gate_on and k > 1:
         # a k-term product must equal the product of its k single pairings, taken from a
         # separate single-pairing launch: compare through a second product with permuted terms
         perm = torch.arange(k - 1, -1, -1, device="cuda")
@@ -470,7 +507,7 @@ def main():
         return
     evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
     # The W untimed warm-up steps run HERE, directly before the timed region, and are topped up to at least 0.3 s of
-    # launches: the shader clock falls back while the gate above compares on the host and needs tens of milliseconds of
+    # launches: the shader clock falls back while the gate above (--full) compares on the host and needs tens of milliseconds of
     # load to climb again -- round 6 measured the same 31.6 M cycles per d159 launch take 15.8, 14.5, 13.5, 13.2, 13.2 ms
     # over the first five launches after an idle gap (GRBM_GUI_ACTIVE: 2.01 -> 2.38 GHz; profiles/r06_notes.md), which a
     # 14 ms kernel timed over a handful of steps shows and an 80 ms one does not.
@@ -481,8 +518,8 @@ def main():
         if spun >= max(1, args.warmup):
             torch.cuda.synchronize()
     sync_all()
-    sampler = ClockSampler(dev_index)
-    with sampler:
+    sampler = ClockSampler(dev_index) if args.full else None
+    with sampler or contextlib.nullcontext():
         t0 = time.perf_counter()
         for a, b in evs:
             a.record(stream)
@@ -490,6 +527,8 @@ def main():
             b.record(stream)
         sync_all()
         dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"gt": GT})      # element_to_bytes records of GT, one row per unit of the last step
     kern_ms = [a.elapsed_time(b) for a, b in evs]
     my_kern_ms = sum(kern_ms) / len(kern_ms)
     per_rank_ms = [my_kern_ms]
@@ -500,13 +539,13 @@ def main():
         per_rank_ms = [None] * world
         dist.all_gather_object(per_rank_ms, my_kern_ms)        # a slow rank must be visible in the line rank 0 prints
     per_rank_gate = [{"first_unit": first, "units": n, "checked": gated_units}]
-    if dist is not None:
+    if dist is not None and args.full:
         per_rank_gate = [None] * world
         dist.all_gather_object(per_rank_gate, {"first_unit": first, "units": n, "checked": gated_units})
 
     # the host-buffer entry point (what the PBC glue calls): pinned host memory in, host memory out, PCIe included
     host_path = None
-    if rank == 0 and pp is None and not args.no_host_path:
+    if rank == 0 and pp is None and args.full and not args.no_host_path:
         import ctypes
         h1, h2 = G1.cpu().pin_memory(), G2.cpu().pin_memory()
         hout = torch.empty(n, LT, dtype=torch.uint8).pin_memory()
@@ -539,8 +578,6 @@ def main():
         if pp is not None:
             macs_per_unit = pairing.algorithmic_macs_per_unit(-1)   # the reference's pp_apply algorithm
         exe_per_unit = executed_macs(args.workload)
-        # live probes of the multiply-add pipe (register-only v_mad_u64_u32 chains with an SGPR factor)
-        peak_measured = max(pbc_amd.int_mac_peak(13, 4000)[0], pbc_amd.int_mac_peak(14, 4000)[0])
         alg_rate = n * macs_per_unit / avg_kern_s
         exe_rate = n * exe_per_unit / avg_kern_s if exe_per_unit else None
         basis = "executed" if exe_rate is not None and exe_rate < alg_rate else "algorithmic"
@@ -569,10 +606,7 @@ def main():
                        "parallelism": "range-split x%d, no collectives" % world,
                        **({"param_extra": args.param_extra} if args.param_extra else {})},
             "per_rank_kernel_ms": [round(float(x), 3) for x in per_rank_ms],
-            "per_rank_gate": per_rank_gate,      # every rank's shard is checked before timing (units compared bit for bit)
             "kernel_only": {"value": round(n / avg_kern_s, 1), "unit": unit_name + " per GPU, events around the launch on rank 0"},
-            "host_path": host_path,
-            "clocks": sampler.summary(),         # rank 0's card while the timed steps ran (null where sysfs has no amdgpu files)
             "roofline": {
                 "bound": "valu-int32-mac",   # integer VALU throughput bounds this path, not HBM/MFMA
                 "achieved": round(rate / 1e12, 4),
@@ -582,7 +616,6 @@ def main():
                 # the smaller of the two work models: never credits multiply-adds the kernel did not execute, nor
                 # executed ones beyond what the reference's algorithm needs
                 "frac_basis": basis,
-                "peak_measured": round(peak_measured / 1e12, 4),
                 "algorithmic": {"macs_per_unit": macs_per_unit, "achieved": round(alg_rate / 1e12, 4),
                                 "frac": round(alg_rate / MAC_PEAK, 4),
                                 "note": "the reference algorithm's F_q products x (2 N^2 + N) word multiply-adds (SURVEY 8d)"},
@@ -598,7 +631,14 @@ def main():
                         "algorithmic_bytes_per_unit": unit_bytes},
             },
         }
-        if world == 1:
+        if args.full:
+            out["per_rank_gate"] = per_rank_gate     # every rank's shard is checked before timing (units compared bit for bit)
+            out["host_path"] = host_path
+            out["clocks"] = sampler.summary()       # rank 0's card while the timed steps ran (null where sysfs has no amdgpu files)
+            # live probes of the multiply-add pipe (register-only v_mad_u64_u32 chains with an SGPR factor)
+            peak_measured = max(pbc_amd.int_mac_peak(13, 4000)[0], pbc_amd.int_mac_peak(14, 4000)[0])
+            out["roofline"]["peak_measured"] = round(peak_measured / 1e12, 4)
+        if world == 1 and args.full:
             cb = None if args.no_cpu_baseline else cpu_baseline(param_path, k, fixture, pp=args.workload.endswith("-pp"))
             out["cpu_baseline"] = cb if cb is not None else container_cpu_baseline(args.workload)
         if evidence_commit():

@@ -31,7 +31,7 @@ def test_bench_strong_scaling_two_ranks_share_the_gpu(workload, log2n, k):
     env = dict(os.environ, PBC_BENCH_SAME_DEVICE="1", PBC_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29533", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--workload", workload, "--strong", "--log2n", str(log2n), "--no-cpu-baseline", "--no-host-path"]
+           "--workload", workload, "--strong", "--log2n", str(log2n), "--no-cpu-baseline", "--no-host-path", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -55,7 +55,7 @@ def test_bench_strong_scaling_eight_ranks_ragged_job():
     env = dict(os.environ, PBC_BENCH_SAME_DEVICE="1", PBC_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
            "--master-port", "29541", os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1",
-           "--workload", "a-prod16", "--strong", "--log2n", "11", "--extra-units", "5", "--no-cpu-baseline", "--no-host-path"]
+           "--workload", "a-prod16", "--strong", "--log2n", "11", "--extra-units", "5", "--no-cpu-baseline", "--no-host-path", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=1200, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -995,6 +995,42 @@ def test_bench_two_ranks_share_the_gpu(tmp_path):
     assert j["value"] > 0 and j["scaling"] == "weak"
 
 
+def test_bench_plain_run_dumps_what_its_last_step_computed(tmp_path):
+    """a plain `bench.py --steps K --warmup W --dump-outputs DIR` (no --full: no gate, no side measurements) prints the line
+    with `ms_per_step` and writes a fixed sample of the last step's GT records as float32: the sampled rows that pair P_a
+    with Q_a must be the reference's e(P_a, Q_a) from the fixture, and a second run writes the same rows"""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    outs = []
+    for rep in range(2):
+        d = tmp_path / ("run%d" % rep)
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--log2n", "18",
+               "--dump-outputs", str(d)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        j = json.loads(lines[0])
+        assert j["steps"] == 3 and j["ms_per_step"] > 0 and j["value"] > 0 and j["higher_is_better"] is True
+        assert "cpu_baseline" not in j and "host_path" not in j
+        gt, rows = np.load(d / "gt.npy"), np.load(d / "gt_rows.npy")
+        assert gt.dtype == np.float32 and rows.dtype == np.float64 and gt.shape == (len(rows), 128) and 0 < len(rows) < 1 << 18
+        assert os.path.getsize(d / "gt.npy") + os.path.getsize(d / "gt_rows.npy") <= 64 << 20
+        outs.append((gt, rows))
+    assert np.array_equal(outs[0][0], outs[1][0]) and np.array_equal(outs[0][1], outs[1][1])
+    gt, rows = outs[0]
+    v = golden("a_chain1024.vec")
+    D = len(v.g1)
+    t = rows.astype(np.int64)
+    diag = t[(t // D) % D == t % D]
+    assert len(diag) > 0
+    got = gt[np.searchsorted(t, diag)].astype(np.uint8)
+    assert np.array_equal(got, v.gt[(diag // D) % D])
+
+
 @pytest.mark.parametrize("how", ["LD_PRELOAD", "link-wrap"])
 @pytest.mark.parametrize("pname", ["a", "d159", "f"])
 def test_unmodified_program_runs_its_pairings_on_the_gpu(how, pname):
