@@ -267,6 +267,33 @@ int pbc_hip_element_from_bytes_compressed_batch_dev(pbc_hip_pairing_t *p, int gr
 int pbc_hip_element_to_bytes_x_only_batch_dev(pbc_hip_pairing_t *p, int group, void *d_out, const void *d_in, size_t n, void *stream);
 int pbc_hip_element_from_bytes_x_only_batch_dev(pbc_hip_pairing_t *p, int group, void *d_out, const void *d_in, size_t n, void *stream);
 
+/* Verdicts: is_almost_coddh (include/pbc_pairing.h:240-243; the pairing->is_almost_coddh hook, include/pbc_pairing.h:34;
+ * generic_is_almost_coddh ecc/pairing.c:15-33, the versions of types d and g ecc/d_param.c:739-784, ecc/g_param.c:560)
+ * over a batch, decided on the device.  a, b: n records of G1; c, d: n records of G2, in the wire format of
+ * pbc_hip_element_pairing_batch; res: n bytes, each exactly 0 or 1.  With T0 = element_pairing(a_i, d_i) and
+ * T1 = element_pairing(b_i, c_i) as pbc_hip_element_pairing_batch returns them,
+ *   res_i = (T0 == T1)                       PBC_HIP_CODDH_EXACT: the element_cmp of two pairings that ends a verification
+ *                                            (example/bls.c:70-78)
+ *   res_i = (T0 == T1) or (T0 * T1 == 1)     PBC_HIP_CODDH_ALMOST: is_almost_coddh -- what verifies a signature that came
+ *                                            as an x-only record, whose y is known up to its sign (example/bls.c:97-110;
+ *                                            element_from_bytes_x_only above)
+ * Whatever the pairing entry point accepts is accepted here and gives the verdict that follows from its outputs
+ * (coordinates >= q; the identity record, which the reference's versions for types d and g hand to the Miller loop
+ * unguarded, ecc/d_param.c:764: outside its domain, defined here).  Any other mode is an error.
+ * The 2 n pairings run as ONE batch of pbc_hip_element_pairing_batch's own launch path, so the small-batch wave kernels
+ * and the throughput kernels are each used where a pairing batch of 2 n units uses them (a single verdict: two pairings
+ * on the wave kernels).  The 2 n GT records stay in the object's (device, stream) workspace and never cross to the host;
+ * the comparison is on field elements, not on byte or limb images.
+ * Host-buffer form: arguments, n == 0 and the range split over the device set as pbc_hip_element_pairing_batch.
+ * _dev form: device-resident buffers, enqueued on `stream`, asynchronous (the inputs are gathered into the workspace with
+ * stream-ordered device copies first). */
+#define PBC_HIP_CODDH_ALMOST 0   /* e(a,d) == e(b,c)  or  e(a,d) * e(b,c) == 1   (is_almost_coddh) */
+#define PBC_HIP_CODDH_EXACT  1   /* e(a,d) == e(b,c) only (example/bls.c:70-78: element_cmp of two pairings) */
+int pbc_hip_is_almost_coddh_batch(pbc_hip_pairing_t *p, uint8_t *res, const uint8_t *a, const uint8_t *b,
+                                  const uint8_t *c, const uint8_t *d, size_t n, int mode);
+int pbc_hip_is_almost_coddh_batch_dev(pbc_hip_pairing_t *p, void *d_res, const void *d_a, const void *d_b,
+                                      const void *d_c, const void *d_d, size_t n, int mode, void *stream);
+
 /* Fixed-base powers: replace element_pp_init / element_pp_pow_zn / element_pp_clear (include/pbc_field.h:591-625 ->
  * element_build_base_table / element_pow_base_table, arith/field.c:243-323: a table of in^(w 2^(5 i)), a power = a product
  * of table entries) for a base in G1, G2 (group 1, 2) or GT (group 3) -- the BLS shape: one generator, many secret keys or

@@ -130,6 +130,8 @@ def lib():
         L.pbc_hip_element_pairing_batch_limbs.argtypes = [vp, vp, vp, vp, sz]
         L.pbc_hip_element_prod_pairing_batch_limbs.argtypes = [vp, vp, vp, vp, sz, ci]
         L.pbc_hip_element_prod_pairing_batch_limbs_dev.argtypes = [vp, vp, vp, vp, sz, ci, vp]
+        L.pbc_hip_is_almost_coddh_batch.argtypes = [vp] + [vp] * 5 + [sz, ci]
+        L.pbc_hip_is_almost_coddh_batch_dev.argtypes = [vp] + [vp] * 5 + [sz, ci, vp]
         _lib = L
     return _lib
 
@@ -163,6 +165,7 @@ EXPORTS = (
     "pbc_hip_element_pow2_zn_batch", "pbc_hip_element_pow3_zn_batch", "pbc_hip_element_pow2_zn_batch_dev", "pbc_hip_element_pow3_zn_batch_dev",
     "pbc_hip_diag_dw_schedule", "pbc_hip_diag_fw_schedule", "pbc_hip_diag_gw_schedule", "pbc_hip_diag_ag_table", "pbc_hip_fq_limb_image_bytes", "pbc_hip_element_pairing_batch_limbs", "pbc_hip_element_prod_pairing_batch_limbs",
     "pbc_hip_element_prod_pairing_batch_limbs_dev",
+    "pbc_hip_is_almost_coddh_batch", "pbc_hip_is_almost_coddh_batch_dev",
 )
 
 
@@ -177,6 +180,7 @@ def param_text(name):
         return fh.read()
 
 
+CODDH_ALMOST, CODDH_EXACT = 0, 1     # PBC_HIP_CODDH_* (include/pbc_hip.h)
 ZR_OPS = {"mul": 0, "add": 1, "sub": 2, "invert": 3, "neg": 4, "halve": 5, "double": 6, "div": 7}   # pbc_hip_zr_op_batch
 
 
@@ -309,6 +313,27 @@ class Pairing:
     def element_prod_pairing_dev(self, d_gt, d_g1, d_g2, n, k, stream=0):
         if lib().pbc_hip_element_prod_pairing_batch_dev(self._h, d_gt, d_g1, d_g2, n, k, stream):
             raise PbcHipError("element_prod_pairing_dev: " + _err())
+
+    # ---- verdicts: is_almost_coddh over a batch (include/pbc_hip.h) ------------------------------
+    def is_almost_coddh(self, a, b, c, d, exact=False):
+        """res[i] = 1 iff e(a_i, d_i) == e(b_i, c_i), or -- unless ``exact`` -- e(a_i, d_i) e(b_i, c_i) == 1
+        (is_almost_coddh; a, b: records of G1, c, d: records of G2).  Returns an np.uint8 array of shape (n,)."""
+        import numpy as np
+        a, b, c, d = (np.ascontiguousarray(x, dtype=np.uint8) for x in (a, b, c, d))
+        l1, l2 = self.length_in_bytes_G1, self.length_in_bytes_G2
+        n = a.size // l1
+        if a.size != n * l1 or b.size != n * l1 or c.size != n * l2 or d.size != n * l2:
+            raise ValueError("a/b (G1) and c/d (G2) sizes do not describe the same number of elements")
+        res = np.empty(n, np.uint8)
+        mode = CODDH_EXACT if exact else CODDH_ALMOST
+        if lib().pbc_hip_is_almost_coddh_batch(self._h, _np_ptr(res), _np_ptr(a), _np_ptr(b), _np_ptr(c), _np_ptr(d), n, mode):
+            raise PbcHipError("is_almost_coddh: " + _err())
+        return res
+
+    def is_almost_coddh_dev(self, d_res, d_a, d_b, d_c, d_d, n, exact=False, stream=0):
+        mode = CODDH_EXACT if exact else CODDH_ALMOST
+        if lib().pbc_hip_is_almost_coddh_batch_dev(self._h, d_res, d_a, d_b, d_c, d_d, n, mode, stream):
+            raise PbcHipError("is_almost_coddh_dev: " + _err())
 
     # ---- text formats (host side; include/pbc_hip.h) ------------------------------------------
     def _group_len(self, group):

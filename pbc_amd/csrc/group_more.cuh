@@ -225,6 +225,33 @@ PBC_DEV void gt_multi_pow_lane(uint8_t *out, const MultiArgs &M, size_t idx, int
   G::store(out, acc);
 }
 
+// is_almost_coddh (include/pbc_pairing.h:240-243, generic_is_almost_coddh ecc/pairing.c:15-33) on the two pairings of a
+// unit: 1 iff T0 == T1, or -- almost -- T0 T1 == 1 (the reference inverts one side and compares again: e(a,d) e(b,c) = 1).
+// G: GT as a field policy of group_ops.cuh.  The comparison is on VALUES: G::load takes a record into Montgomery words
+// through a product with R^2 (fp_load_be), which reduces any residue, a coordinate >= q included, to [0, q); every word
+// image below is therefore the one image of its field element, and so is the identity's (R mod q).  The product is
+// formed rather than a conjugate compared, so that the answer is the definition's for every record the pairing kernels
+// can emit (the identity record, GT = F_q of type e, elements outside the unitary subgroup).  Both tests are always
+// computed and combined with plain logic: neighbouring lanes hold different verdicts, nothing here branches on one.
+template <class G>
+PBC_DEV uint8_t coddh_verdict_lane(const uint8_t *t0, const uint8_t *t1, bool almost) {
+  typename G::el a, b, p, id;
+  G::load(a, t0);
+  G::load(b, t1);
+  G::mul(p, a, b);
+  G::one(id);
+  uint32_t wa[G::WORDS_EL], wb[G::WORDS_EL];
+  G::to_words(wa, a);
+  G::to_words(wb, b);
+  uint32_t diff = 0, off1 = 0;
+  for (int k = 0; k < G::WORDS_EL; k++) diff |= wa[k] ^ wb[k];
+  G::to_words(wa, p);
+  G::to_words(wb, id);
+  for (int k = 0; k < G::WORDS_EL; k++) off1 |= wa[k] ^ wb[k];
+  const unsigned same = diff == 0, inverse = off1 == 0;
+  return (uint8_t) (same | (inverse & (unsigned) almost));
+}
+
 // Z_r arithmetic on element_to_bytes records: the F_q routines of fp.cuh on a constant block whose modulus is the group
 // order r (the reference runs its F_p back end on r: pairing->Zr).  op 0 mul, 1 add, 2 sub, 3 invert, 4 neg, 5 halve,
 // 6 double, 7 div (a / b), 8 element_from_hash (a: a digest of hlen bytes; fp_from_hash arith/montfp.c:440-448)

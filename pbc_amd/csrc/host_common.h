@@ -163,10 +163,10 @@ unsigned *unit_counter(pbc_hip_pairing_s *P, hipStream_t s);   // "hip_dynamic 1
 #define PBC_RGRID(...) resident_grid(P, reinterpret_cast<const void *>(&__VA_ARGS__), n)
 void *pinned_dev_ptr(const void *host, size_t bytes, bool shared);
 bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb);
-void *workspace_get(pbc_hip_pairing_s *P, hipStream_t s, size_t bytes);
+void *workspace_get(pbc_hip_pairing_s *P, hipStream_t s, size_t bytes, int part = 0);   // part 1: the entry's second buffer (ProdWs::get2)
 void workspace_unpin(pbc_hip_pairing_s *P, hipStream_t s);
 // A workspace that belongs to one stream of a device context of the host-buffer path: grown on demand, freed with the context.
-struct OwnWs { void **p; size_t *cap; };
+struct OwnWs { void **p; size_t *cap; void **p2; size_t *cap2; };     // (p2 / cap2: the second buffer, ProdWs::get2)
 void *own_workspace(const OwnWs &o, hipStream_t s, size_t bytes);
 void *object_scratch(pbc_hip_pairing_s *P, const void *key, size_t bytes, bool *fresh);    // small per-(device, key) buffers the object keeps (pbc_hip.hip)
 // The workspace of one product launch: the caller's own (host-buffer path) or the object's table entry for (device,
@@ -187,12 +187,25 @@ struct ProdWs {
     pinned = pinned || w != nullptr;
     return w;
   }
+  // A second buffer of the same workspace, for a call that keeps intermediates of its own ACROSS a launcher that asks
+  // get() for what its kernels need (is_almost_coddh: the GT records of its 2 n pairings): the two requests must not
+  // share bytes, and a launcher's request may grow -- move -- the first buffer.  Same entry, same pin, same issue lock.
+  void *get2(size_t bytes) {
+    if (own) { const OwnWs second = {own->p2, own->cap2, nullptr, nullptr}; return own_workspace(second, s, bytes); }
+    void *w = workspace_get(P, s, bytes, 1);
+    if (w && pinned) workspace_unpin(P, s);
+    pinned = pinned || w != nullptr;
+    return w;
+  }
 };
 // The host-buffer path (pbc_hip.hip): chunks over the device set, page-locked buffers in place, anything else staged
 // through per-device chunk buffers that the object keeps.  `launch` enqueues one chunk (device pointers) on a stream.
 typedef std::function<int(void *d_out, const void *d_a, const void *d_b, size_t m, hipStream_t s, const OwnWs *own)> ChunkLaunch;
 int run_host_generic(pbc_hip_pairing_s *P, uint8_t *out, size_t ut, const uint8_t *a, size_t u1, const uint8_t *b, size_t u2,
                      size_t n, const ChunkLaunch &launch, bool zero_copy_ok);
+// n single pairings on stream s through the launch path of element_pairing_batch (pbc_hip.hip launch_prod, k = 1: wave
+// routes and lane kernels are chosen there); constants already derived
+int launch_pairings(pbc_hip_pairing_s *P, void *d_gt, const void *d_g1, const void *d_g2, size_t n, hipStream_t s, const OwnWs *own);
 // Per-family launchers: k-term products (k = 1: single pairings) of n units on stream s; constants already derived.
 int launch_a(pbc_hip_pairing_s *P, void *d_gt, const void *d_g1, const void *d_g2, size_t n, int k, hipStream_t s, ProdWs &W);   // pbc_hip_a.hip: a, a1, e
 int launch_d(pbc_hip_pairing_s *P, void *d_gt, const void *d_g1, const void *d_g2, size_t n, int k, hipStream_t s, ProdWs &W);   // pbc_hip_d.hip: d, g

@@ -547,6 +547,8 @@ struct DevCtx {
   size_t cap1[kSlots] = {0, 0, 0}, cap2[kSlots] = {0, 0, 0}, capt[kSlots] = {0, 0, 0};   // bytes of each slot's chunk buffers (slots are allocated when first used)
   void *ws[kSlots] = {nullptr, nullptr, nullptr};                                          // product workspace of each slot's stream (launch_prod)
   size_t wscap[kSlots] = {0, 0, 0};
+  void *ws2[kSlots] = {nullptr, nullptr, nullptr};                                         // ... and its second buffer (ProdWs::get2)
+  size_t ws2cap[kSlots] = {0, 0, 0};
 };
 // Workspaces of the product kernels (per-term Miller state).  The host-buffer path owns one per stream of its device
 // contexts (DevCtx::ws: they live and die with the streams).  Launches of the *_dev entry points on CALLER streams get one
@@ -557,7 +559,8 @@ struct DevCtx {
 // `issue` is held from workspace_get to workspace_unpin, i.e. while ONE call enqueues its kernels: two host threads that
 // launch on the same (object, stream) pair take turns, so the complete pass of a two-pass operation always reads the flags
 // its own fast pass wrote (the stream runs each call's kernels back to back).  Recursive: a call may ask twice.
-struct WsEnt { int dev; hipStream_t st; void *p; size_t cap; uint64_t used; int pins; std::recursive_mutex issue; };
+// p2 / cap2: the entry's second buffer (ProdWs::get2: intermediates a composed call keeps across a launcher's own request).
+struct WsEnt { int dev; hipStream_t st; void *p; size_t cap; uint64_t used; int pins; std::recursive_mutex issue; void *p2 = nullptr; size_t cap2 = 0; };
 constexpr size_t kMaxWs = 8;
 // Small device buffers that belong to the object and a device, kept until the object is cleared: the schedule of the type d
 // wave kernel (read-only, shared by every launch), the wire-format staging area of the limb-image host calls.  Plain
@@ -588,8 +591,9 @@ static void devctx_free_buffers(DevCtx &c) {   // the calling thread's current d
     if (c.d2[i]) (void) hipFree(c.d2[i]);
     if (c.dt[i]) (void) hipFree(c.dt[i]);
     if (c.ws[i]) (void) hipFree(c.ws[i]);
-    c.d1[i] = c.d2[i] = c.dt[i] = c.ws[i] = nullptr;
-    c.cap1[i] = c.cap2[i] = c.capt[i] = c.wscap[i] = 0;
+    if (c.ws2[i]) (void) hipFree(c.ws2[i]);
+    c.d1[i] = c.d2[i] = c.dt[i] = c.ws[i] = c.ws2[i] = nullptr;
+    c.cap1[i] = c.cap2[i] = c.capt[i] = c.wscap[i] = c.ws2cap[i] = 0;
   }
 }
 static void devctx_release(DevCtx &c) {
@@ -615,6 +619,7 @@ static void hostctx_free(pbc_hip_pairing_s *P) {
     DeviceGuard guard(w->dev);
     (void) hipDeviceSynchronize();
     (void) hipFree(w->p);
+    (void) hipFree(w->p2);
   }
   scratch_free_all(H);
   for (int i = 0; i < H->n; i++) devctx_release(H->dc[i]);
@@ -624,7 +629,7 @@ static void hostctx_free(pbc_hip_pairing_s *P) {
 // At least `bytes` of device memory for a kernel about to be launched on stream `s` of the current device; kept by the
 // object, grown on demand (the only allocation a steady-state call can make).  The entry is PINNED until
 // workspace_unpin: an entry whose kernel has not been enqueued yet is never evicted.
-void *workspace_get(pbc_hip_pairing_s *P, hipStream_t s, size_t bytes) {
+void *workspace_get(pbc_hip_pairing_s *P, hipStream_t s, size_t bytes, int part) {
   int dev = -1;
   if (hipGetDevice(&dev) != hipSuccess) { fail("no current HIP device"); return nullptr; }
   if (!P->host_ctx) P->host_ctx = new HostCtx();
@@ -644,29 +649,32 @@ void *workspace_get(pbc_hip_pairing_s *P, hipStream_t s, size_t bytes) {
             DeviceGuard guard(H->ws[lru]->dev);
             (void) hipDeviceSynchronize();
             if (H->ws[lru]->p) (void) hipFree(H->ws[lru]->p);
+            if (H->ws[lru]->p2) (void) hipFree(H->ws[lru]->p2);
           }
           H->ws.erase(H->ws.begin() + (long) lru);
         }                                  // (every entry pinned: the table grows past kMaxWs for the moment)
       }
-      H->ws.emplace_back(new WsEnt{dev, s, nullptr, 0, 0, 0, {}});
+      H->ws.emplace_back(new WsEnt{dev, s, nullptr, 0, 0, 0, {}, nullptr, 0});
       e = H->ws.back().get();
     }
     e->used = ++H->ws_clock;
     e->pins++;
   }
   e->issue.lock();                         // (outside the table lock: another thread may be enqueueing on this entry)
-  if (e->cap < bytes) {
-    if (e->p) { (void) hipStreamSynchronize(s); (void) hipFree(e->p); e->p = nullptr; e->cap = 0; }
-    if (hipMalloc(&e->p, bytes) != hipSuccess) {
-      e->p = nullptr;
+  void *&buf = part ? e->p2 : e->p;
+  size_t &cap = part ? e->cap2 : e->cap;
+  if (cap < bytes) {
+    if (buf) { (void) hipStreamSynchronize(s); (void) hipFree(buf); buf = nullptr; cap = 0; }
+    if (hipMalloc(&buf, bytes) != hipSuccess) {
+      buf = nullptr;
       e->issue.unlock();
       { std::lock_guard<std::mutex> lk(H->mu); e->pins--; }
       fail("device allocation of a %zu-byte product workspace failed", bytes);
       return nullptr;
     }
-    e->cap = bytes;
+    cap = bytes;
   }
-  return e->p;
+  return buf;
 }
 void workspace_unpin(pbc_hip_pairing_s *P, hipStream_t s) {
   int dev = -1;
@@ -717,6 +725,7 @@ extern "C" int pbc_hip_pairing_release_workspaces(pbc_hip_pairing_t *P) {
     DeviceGuard guard(w->dev);
     (void) hipDeviceSynchronize();
     if (w->p) (void) hipFree(w->p);
+    if (w->p2) (void) hipFree(w->p2);
   }
   H->ws.clear();
   scratch_free_all(H);
@@ -817,7 +826,7 @@ int run_host_generic(pbc_hip_pairing_s *P, uint8_t *gt, size_t ut, const uint8_t
     if (!c) return;
     size_t round = 0;
     if (zc) {                            // the kernels work on the caller's pinned buffers: no staging copies
-      const OwnWs own = {&c->ws[0], &c->wscap[0]};
+      const OwnWs own = {&c->ws[0], &c->wscap[0], &c->ws2[0], &c->ws2cap[0]};
       for (size_t idx = (size_t) d; idx < nchunks; idx += (size_t) ndev) {
         const size_t off = idx * chunk, m = n - off < chunk ? n - off : chunk;
         if (launch(zt + off * ut, z1 + off * u1, z2 ? z2 + off * u2 : nullptr, m, c->st[0], &own)) { *err = g_err; break; }
@@ -831,7 +840,7 @@ int run_host_generic(pbc_hip_pairing_s *P, uint8_t *gt, size_t ut, const uint8_t
       const size_t off = idx * chunk, m = n - off < chunk ? n - off : chunk;
       hipStream_t st = c->st[sl];
       if (!devctx_slot(c, sl, chunk * u1, g2 ? chunk * u2 : 0, chunk * ut, *err)) break;
-      const OwnWs own = {&c->ws[sl], &c->wscap[sl]};
+      const OwnWs own = {&c->ws[sl], &c->wscap[sl], &c->ws2[sl], &c->ws2cap[sl]};
       if (hipMemcpyAsync(c->d1[sl], g1 + off * u1, m * u1, hipMemcpyHostToDevice, st) != hipSuccess ||
           (g2 && hipMemcpyAsync(c->d2[sl], g2 + off * u2, m * u2, hipMemcpyHostToDevice, st) != hipSuccess)) { *err = "H2D copy failed"; break; }
       if (launch(c->dt[sl], c->d1[sl], g2 ? c->d2[sl] : nullptr, m, st, &own)) { *err = g_err; break; }
@@ -886,6 +895,9 @@ static int launch_prod(pbc_hip_pairing_s *P, void *d_gt, const void *d_g1, const
   if (P->type == 'd' || P->type == 'g') return launch_d(P, d_gt, d_g1, d_g2, n, k, s, W);
   if (P->type == 'f') return launch_f(P, d_gt, d_g1, d_g2, n, k, s, W);
   return fail("unsupported type");
+}
+int launch_pairings(pbc_hip_pairing_s *P, void *d_gt, const void *d_g1, const void *d_g2, size_t n, hipStream_t s, const OwnWs *own) {
+  return launch_prod(P, d_gt, d_g1, d_g2, n, 1, s, false, own);
 }
 extern "C" int pbc_hip_element_prod_pairing_batch_dev(pbc_hip_pairing_t *P, void *d_gt, const void *d_g1,
                                                       const void *d_g2, size_t n, int k, void *stream) {

@@ -1,5 +1,6 @@
 // pbc_hip_group.hip -- kernels and C-ABI entry points of the group operations next to the pairing: libpbc_hip.so; see host_common.h
 #include "host_common.h"
+#include "group_more.cuh"
 
 // ---- group operations (one element per lane) -------------------------------------------------
 // element_mul_zn: the COMPLETE ladder (ec_mul_lane: any point, any scalar, two group operations per bit) over a field
@@ -256,6 +257,34 @@ __global__ void __launch_bounds__(kBlock, 2) gt_op_kernel(int type, int op, uint
 }
 
 
+// is_almost_coddh: one unit per lane -- the two GT records of the unit (record i of t0 / t1 at i * stride) -> one byte, 0 or 1
+// (group_more.cuh coddh_verdict_lane; the type dispatch of gt_op_kernel)
+template <int N>
+__global__ void __launch_bounds__(kBlock, 2) coddh_verdict_kernel(int type, int almost, uint8_t *res, const uint8_t *t0, const uint8_t *t1,
+                                                                   size_t stride, size_t n, KArgs<N> ka) {
+  size_t idx = (size_t) blockIdx.x * kBlock + threadIdx.x;
+  if (idx >= n) return;
+  const uint8_t *x = t0 + idx * stride, *y = t1 + idx * stride;
+  const bool al = almost != 0;
+  uint8_t v = 0;
+  if constexpr (N == 16 || N == 33) {
+    if (type == 'e') v = coddh_verdict_lane<GtE<N>>(x, y, al);       // GT = F_q: no conjugate, the product decides
+    else v = coddh_verdict_lane<GtA<N>>(x, y, al);
+  } else {
+    if (type == 'd') {
+      if constexpr (N <= ND_MAX) v = coddh_verdict_lane<GtD<N, 3>>(x, y, al);
+    } else if constexpr (N == 5 || N == 8) {
+      if (type == 'g') {
+        if constexpr (N == 5) v = coddh_verdict_lane<GtD<N, 5>>(x, y, al);
+      } else {
+        v = coddh_verdict_lane<GtF<N>>(x, y, al);
+      }
+    }
+  }
+  res[idx] = v;
+}
+
+
 // ---------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------
@@ -501,6 +530,78 @@ extern "C" int pbc_hip_element_from_bytes_x_only_batch(pbc_hip_pairing_t *P, int
 }
 extern "C" int pbc_hip_element_from_bytes_x_only_batch_dev(pbc_hip_pairing_t *P, int group, void *d_out, const void *d_in, size_t n, void *stream) {
   return group_dev(P, G_FROM_X, group, 0, d_out, d_in, nullptr, n, stream);
+}
+
+// ---- is_almost_coddh (include/pbc_pairing.h:240-243; ecc/pairing.c:15-33, ecc/d_param.c:739-784) ------------------------
+// n units = 2 n single pairings in ONE call of the pairings' own launcher (launch_pairings, pbc_hip.hip: the wave routes
+// and the lane kernels are chosen there, by the 2 n), then coddh_verdict_kernel over the 2 n GT records.  The records
+// live in the second buffer of the (device, stream) workspace (ProdWs::get2; the first one is what the pairing kernels
+// themselves ask for), held with its issue lock until the verdict kernel is enqueued; nothing is synchronised.
+// pairs == false (device-buffer form): the four inputs are separate arrays, so a | b and d | c are gathered behind the GT
+// records with stream-ordered device copies, unit i's records are i and n + i.  pairs == true (host-buffer form): the host
+// has packed a_i | b_i and d_i | c_i side by side, the chunk IS an array of 2 m pairings and unit i's records are 2 i, 2 i + 1.
+static size_t ws_round(size_t b) { return (b + 255) & ~(size_t) 255; }
+static int coddh_launch(pbc_hip_pairing_s *P, int mode, bool pairs, void *d_res, const void *d_a, const void *d_b, const void *d_c,
+                        const void *d_d, size_t n, hipStream_t s, const OwnWs *own) {
+  if (!n) return 0;
+  const size_t l1 = (size_t) P->len1, l2 = (size_t) P->len2, lt = (size_t) P->lenT;
+  const size_t gt_bytes = ws_round(2 * n * lt), g1_bytes = ws_round(2 * n * l1), g2_bytes = 2 * n * l2;
+  ProdWs W(P, s, own);
+  uint8_t *gt = (uint8_t *) W.get2(pairs ? gt_bytes : gt_bytes + g1_bytes + g2_bytes);
+  if (!gt) return 1;
+  const void *g1 = d_a, *g2 = d_d;       // pairs: a_i | b_i and d_i | c_i as the chunk holds them
+  if (!pairs) {
+    uint8_t *p1 = gt + gt_bytes, *p2 = p1 + g1_bytes;
+    HIP_TRY(hipMemcpyAsync(p1, d_a, n * l1, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(p1 + n * l1, d_b, n * l1, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(p2, d_d, n * l2, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(p2 + n * l2, d_c, n * l2, hipMemcpyDeviceToDevice, s));
+    g1 = p1;
+    g2 = p2;
+  }
+  if (launch_pairings(P, gt, g1, g2, 2 * n, s, own)) return 1;
+  const unsigned grid = (unsigned) ((n + kBlock - 1) / kBlock);
+  const uint8_t *t1 = pairs ? gt + lt : gt + n * lt;
+  const size_t stride = pairs ? 2 * lt : lt;
+  PBC_DISPATCH_N(P->nlimb, hipLaunchKernelGGL(coddh_verdict_kernel<N>, dim3(grid), dim3(kBlock), 0, s, P->type, mode == PBC_HIP_CODDH_ALMOST ? 1 : 0,
+                                              (uint8_t *) d_res, (const uint8_t *) gt, t1, stride, n, kargs<N>(P)));
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+static int coddh_check(const pbc_hip_pairing_s *P, int mode) {
+  if (!P) return fail("null pairing");
+  if (mode != PBC_HIP_CODDH_ALMOST && mode != PBC_HIP_CODDH_EXACT) return fail("is_almost_coddh: mode must be PBC_HIP_CODDH_ALMOST or PBC_HIP_CODDH_EXACT");
+  if (P->device < 0) return fail("no HIP device: libpbc_hip has no CPU fallback");
+  return 0;
+}
+extern "C" int pbc_hip_is_almost_coddh_batch_dev(pbc_hip_pairing_t *P, void *d_res, const void *d_a, const void *d_b, const void *d_c,
+                                                 const void *d_d, size_t n, int mode, void *stream) {
+  if (coddh_check(P, mode)) return 1;
+  if (!n) return 0;
+  if (!d_res || !d_a || !d_b || !d_c || !d_d) return fail("null argument");
+  if (ensure_derived(P, (hipStream_t) stream)) return 1;
+  return coddh_launch(P, mode, false, d_res, d_a, d_b, d_c, d_d, n, (hipStream_t) stream, nullptr);
+}
+// host buffers: a_i | b_i and d_i | c_i packed side by side (as the multi-exponentiations pack their bases), so that the
+// host-buffer path of the pairings -- device set, range split, chunk ring -- serves the call as one two-input operation
+// with one result byte per unit
+extern "C" int pbc_hip_is_almost_coddh_batch(pbc_hip_pairing_t *P, uint8_t *res, const uint8_t *a, const uint8_t *b, const uint8_t *c,
+                                             const uint8_t *d, size_t n, int mode) {
+  if (coddh_check(P, mode)) return 1;
+  if (!n) return 0;
+  if (!res || !a || !b || !c || !d) return fail("null argument");
+  const size_t l1 = (size_t) P->len1, l2 = (size_t) P->len2;
+  std::vector<uint8_t> A(2 * n * l1), D(2 * n * l2);
+  for (size_t i = 0; i < n; i++) {
+    memcpy(&A[2 * i * l1], a + i * l1, l1);
+    memcpy(&A[(2 * i + 1) * l1], b + i * l1, l1);
+    memcpy(&D[2 * i * l2], d + i * l2, l2);
+    memcpy(&D[(2 * i + 1) * l2], c + i * l2, l2);
+  }
+  return run_host_generic(P, res, 1, A.data(), 2 * l1, D.data(), 2 * l2, n,
+                          [P, mode](void *d_res, const void *d_ab, const void *d_dc, size_t m, hipStream_t s, const OwnWs *own) {
+                            return coddh_launch(P, mode, true, d_res, d_ab, nullptr, nullptr, d_dc, m, s, own);
+                          }, false);
 }
 
 // ---- fixed-base powers: element_pp_init / element_pp_pow_zn / element_pp_clear (include/pbc_field.h:591-625) -----------
