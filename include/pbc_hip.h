@@ -76,6 +76,7 @@ typedef struct pbc_hip_pairing_s pbc_hip_pairing_t;
  *   hip_host_chunk N     host-buffer calls: units per staged chunk
  *   hip_prod_shared 1    type a products: one product per lane with shared squarings (the reference's shape) instead of
  *                        one term per lane;  hip_prod_chunk N: terms per launch of the one-term-per-lane kernels
+ *   hip_ragged_fold N    ragged products: records a fold lane multiplies, 2 <= N <= 64 (default 16)
  *   hip_group_slow 1     group operations: only the complete ladders / generic powers (no fast pass)
  *   hip_no_limb 1        types d, f: word-form steps on E(F_q) in the pairing kernels, word-form ladders on G1
  *   hip_no_xs 1, hip_no_bm1 1, hip_no_cyc 1, hip_no_bn 1
@@ -163,6 +164,49 @@ int pbc_hip_element_prod_pairing_batch(pbc_hip_pairing_t *p, uint8_t *gt, const 
                                        const uint8_t *g2, size_t n, int k);
 int pbc_hip_element_prod_pairing_batch_dev(pbc_hip_pairing_t *p, void *d_gt, const void *d_g1,
                                            const void *d_g2, size_t n, int k, void *stream);
+/* Ragged products: element_prod_pairing (include/pbc_pairing.h:153-171 -> pairing->prod_pairings: a_pairings_affine
+ * ecc/a_param.c:1283-1383, generic_prod_pairings ecc/pairing.c:35-46) with a term count PER PRODUCT -- committees of
+ * different sizes, one aggregate over thousands of (H(m_i), pk_i) pairs -- in one call:
+ *     gt[u] = to_bytes( prod_{offsets[u] <= t < offsets[u+1]} e(g1[t], g2[t]) ),   u < n.
+ * offsets: n + 1 values in HOST memory in both forms, offsets[0] == 0, non-decreasing; T = offsets[n] is the number of
+ * term records in g1 / g2.  The array is read before the call returns -- also by the asynchronous _dev form -- and may
+ * be freed or overwritten at once.  Per product the semantics of element_prod_pairing: a term whose G1 or G2 record
+ * deserialises to O (off the curve or all zero: "input classes" above) makes THAT product the identity of GT
+ * (include/pbc_pairing.h:161-168) and no other; an empty product (offsets[u] == offsets[u+1]) is the identity, what the
+ * reference's prod_pairings leave for zero terms (generic_prod_pairings sets out to 1 first, ecc/pairing.c:35-46).  The
+ * bytes are those of pbc_hip_element_prod_pairing_batch on the same terms.  Every type: a, a1, d, e, f, g.
+ * (One record is stricter here: on type a with a 512-bit q the all-zero G2 record is the finite point (0, 0), whose
+ * pairing value is 1; the uniform entry point multiplies that 1 into a product of several terms, this one makes the
+ * product the identity, as "zero-filled records" above says.)
+ * A product is reduced in parallel: level by level every lane multiplies up to F consecutive records of one product
+ * (and ANDs their validity) until no product holds more than F; a finish lane multiplies the rest.  The dependent chain
+ * of a product of k terms is O(F log_F k) instead of k; products of at most F terms take no fold level.  Type a with a
+ * 512-bit q folds the 160-byte Miller records of its one-term-per-lane kernel and runs ONE final exponentiation per
+ * product; every other family runs the T terms as single pairings (the launch path of pbc_hip_element_pairing_batch, wave
+ * kernels included) and folds GT values, validity in a byte per record: one final exponentiation per TERM.
+ * F: "hip_ragged_fold N" in the parameter text, 2 <= N <= 64 (default 16; every value gives the same bytes).
+ * Errors (non-zero, pbc_hip_last_error names the cause; checked before the device, so they are reported without one):
+ * null arguments, offsets[0] != 0, a decreasing pair of offsets, a single product of more than 2^22 terms (the
+ * workspace bound below).  n == 0 returns 0.  A call with T > 2^22 is cut into launch groups at product boundaries.
+ * Workspace: the second buffer of the (device, stream) entry below -- the plan (levels x (n + 1) offsets), T records and
+ * T / F more -- and a page-locked staging area for the plan; no allocation in the steady state, no stream-ordered allocator.
+ * Host-buffer form: always staged through the object's chunk buffers; over a device set the products are split into
+ * contiguous ranges balanced by TERM count (a device may be listed twice).  gt may not overlap g1 / g2 usefully (the
+ * record sizes differ); an overlapping output is collected in a buffer of its own first.
+ * _dev form: device-resident gt / g1 / g2, enqueued on `stream`, asynchronous; calls enqueued back to back on one stream
+ * with different offsets are independent (a plan is uploaded in stream order from staging that is not rewritten while a
+ * copy still reads it). */
+int pbc_hip_element_prod_pairing_ragged_batch(pbc_hip_pairing_t *p, uint8_t *gt, const uint8_t *g1, const uint8_t *g2,
+                                              const uint64_t *offsets, size_t n);
+int pbc_hip_element_prod_pairing_ragged_batch_dev(pbc_hip_pairing_t *p, void *d_gt, const void *d_g1, const void *d_g2,
+                                                  const uint64_t *offsets /* HOST memory */, size_t n, void *stream);
+/* The plan of such a call (pure host code; the tests' view of the planner that stands for the loop over the terms in
+ * generic_prod_pairings, ecc/pairing.c:35-46): per level its length (n + 1) followed by its offsets, level 0 -- the
+ * caller's array -- first, then one array per fold level: level i + 1 holds the prefix sums of ceil(c / F) over the
+ * counts c of level i, and the last level has every count <= F.  Returns the number of values of the whole plan (at
+ * most `cap` are written to out, which may be null); 0 for arguments the entry points refuse. */
+size_t pbc_hip_diag_ragged_plan(pbc_hip_pairing_t *p, const uint64_t *offsets, size_t n, uint64_t *out, size_t cap);
+
 /* The product kernels of types a, d and g use a device workspace: one buffer per (device, stream) a *_dev product call was
  * enqueued on, grown on demand and kept by the object.  Types d / g keep the Miller state of every term there:
  * ceil(n / 128) * 128 * k * R  bytes with R = 4 (2 d N + 5 L) (N words and L 29-bit limbs per F_q element, d = 3 or 5 --

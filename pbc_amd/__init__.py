@@ -132,6 +132,10 @@ def lib():
         L.pbc_hip_element_prod_pairing_batch_limbs_dev.argtypes = [vp, vp, vp, vp, sz, ci, vp]
         L.pbc_hip_is_almost_coddh_batch.argtypes = [vp] + [vp] * 5 + [sz, ci]
         L.pbc_hip_is_almost_coddh_batch_dev.argtypes = [vp] + [vp] * 5 + [sz, ci, vp]
+        L.pbc_hip_element_prod_pairing_ragged_batch.argtypes = [vp, vp, vp, vp, vp, sz]
+        L.pbc_hip_element_prod_pairing_ragged_batch_dev.argtypes = [vp, vp, vp, vp, vp, sz, vp]
+        L.pbc_hip_diag_ragged_plan.restype = sz
+        L.pbc_hip_diag_ragged_plan.argtypes = [vp, vp, sz, vp, sz]
         _lib = L
     return _lib
 
@@ -166,6 +170,7 @@ EXPORTS = (
     "pbc_hip_diag_dw_schedule", "pbc_hip_diag_fw_schedule", "pbc_hip_diag_gw_schedule", "pbc_hip_diag_ag_table", "pbc_hip_fq_limb_image_bytes", "pbc_hip_element_pairing_batch_limbs", "pbc_hip_element_prod_pairing_batch_limbs",
     "pbc_hip_element_prod_pairing_batch_limbs_dev",
     "pbc_hip_is_almost_coddh_batch", "pbc_hip_is_almost_coddh_batch_dev",
+    "pbc_hip_element_prod_pairing_ragged_batch", "pbc_hip_element_prod_pairing_ragged_batch_dev", "pbc_hip_diag_ragged_plan",
 )
 
 
@@ -313,6 +318,54 @@ class Pairing:
     def element_prod_pairing_dev(self, d_gt, d_g1, d_g2, n, k, stream=0):
         if lib().pbc_hip_element_prod_pairing_batch_dev(self._h, d_gt, d_g1, d_g2, n, k, stream):
             raise PbcHipError("element_prod_pairing_dev: " + _err())
+
+    # ---- ragged products: a term count per product (include/pbc_hip.h) ---------------------------
+    @staticmethod
+    def _ragged_offsets(offsets):
+        import numpy as np
+        off = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
+        if off.size < 1:
+            raise ValueError("offsets needs n + 1 values")
+        return off
+
+    def element_prod_pairing_ragged(self, g1, g2, offsets):
+        """gt[u] = prod of e(g1[t], g2[t]) over offsets[u] <= t < offsets[u+1]; an empty product and a product with an
+        O term are the identity.  Returns an np.uint8 array of shape (len(offsets) - 1, length_in_bytes_GT)."""
+        import numpy as np
+        g1 = np.ascontiguousarray(g1, dtype=np.uint8)
+        g2 = np.ascontiguousarray(g2, dtype=np.uint8)
+        off = self._ragged_offsets(offsets)
+        n, terms = off.size - 1, int(off[-1])
+        if g1.size != terms * self.length_in_bytes_G1 or g2.size != terms * self.length_in_bytes_G2:
+            raise ValueError("g1 / g2 do not hold offsets[-1] = %d records" % terms)
+        gt = np.empty((n, self.length_in_bytes_GT), np.uint8)
+        # (empty arrays still hand the library a non-null pointer: one spare byte behind the records)
+        if lib().pbc_hip_element_prod_pairing_ragged_batch(self._h, _np_ptr(gt) if n else 1, _np_ptr(g1) if terms else 1,
+                                                           _np_ptr(g2) if terms else 1, _np_ptr(off), n):
+            raise PbcHipError("element_prod_pairing_ragged: " + _err())
+        return gt
+
+    def element_prod_pairing_ragged_dev(self, d_gt, d_g1, d_g2, offsets, stream=0):
+        """the same on device pointers, enqueued on ``stream``; ``offsets`` is a host array and may be reused on return"""
+        off = self._ragged_offsets(offsets)
+        if lib().pbc_hip_element_prod_pairing_ragged_batch_dev(self._h, d_gt, d_g1, d_g2, _np_ptr(off), off.size - 1, stream):
+            raise PbcHipError("element_prod_pairing_ragged_dev: " + _err())
+
+    def ragged_plan(self, offsets):
+        """the planner's level arrays for ``offsets`` (pbc_hip_diag_ragged_plan): a list of np.uint64 arrays, level 0 first"""
+        import numpy as np
+        off = self._ragged_offsets(offsets)
+        need = lib().pbc_hip_diag_ragged_plan(self._h, _np_ptr(off), off.size - 1, None, 0)
+        if not need:
+            raise PbcHipError("ragged_plan: " + _err())
+        out = np.zeros(need, np.uint64)
+        lib().pbc_hip_diag_ragged_plan(self._h, _np_ptr(off), off.size - 1, _np_ptr(out), need)
+        levels, at = [], 0
+        while at < need:
+            m = int(out[at])
+            levels.append(out[at + 1:at + 1 + m].copy())
+            at += 1 + m
+        return levels
 
     # ---- verdicts: is_almost_coddh over a batch (include/pbc_hip.h) ------------------------------
     def is_almost_coddh(self, a, b, c, d, exact=False):

@@ -252,6 +252,51 @@ PBC_DEV uint8_t coddh_verdict_lane(const uint8_t *t0, const uint8_t *t1, bool al
   return (uint8_t) (same | (inverse & (unsigned) almost));
 }
 
+// Ragged products of pairings on GT records (pbc_hip_element_prod_pairing_ragged_batch; every family but the 512-bit
+// type a, whose fold runs on Miller records: pairing_al.cuh fold_lane).  The terms have run as single pairings; the
+// final exponentiation is a homomorphism, so the product of their GT values is element_prod_pairing's value.
+// A pairing with an argument O and a genuine e(P, Q) = 1 give the same bytes, so validity travels next to the values,
+// one byte per record: term_flag_lane writes it from the two input records with the loader of the group operations
+// (ec_load_affine: on the curve and not the all-zero record), the fold ANDs it.
+// F1 / F2: the field policies of G1 / G2 (FqOps; FdOps / Fq2Ops on the twists).
+template <class F1, class F2>
+PBC_DEV uint8_t term_flag_lane(const uint8_t *g1, const uint8_t *g2) {
+  typename F1::el x1, y1;
+  typename F2::el x2, y2;
+  const unsigned a = ec_load_affine<F1>(x1, y1, g1), b = ec_load_affine<F2>(x2, y2, g2);
+  return (uint8_t) (a & b);
+}
+// cnt >= 1 consecutive records of ONE product -> one record and the AND of their flags (the return value)
+template <class G>
+PBC_DEV uint8_t gt_fold_lane(uint8_t *out, const uint8_t *rec, const uint8_t *flags, int cnt) {
+  typename G::el acc, t;
+  G::load(acc, rec);
+  unsigned v = flags[0];
+  const size_t L = (size_t) G::bytes();
+  for (int j = 1; j < cnt; j++) {
+    G::load(t, rec + (size_t) j * L);
+    G::mul(acc, acc, t);
+    v &= flags[j];
+  }
+  G::store(out, acc);
+  return (uint8_t) v;
+}
+// the last cnt >= 0 records of a product -> its GT bytes: the identity for an empty product and for one with an O term
+template <class G>
+PBC_DEV void gt_fold_finish_lane(uint8_t *gt, const uint8_t *rec, const uint8_t *flags, int cnt) {
+  typename G::el acc, t;
+  G::one(acc);
+  unsigned v = cnt > 0;
+  const size_t L = (size_t) G::bytes();
+  for (int j = 0; j < cnt; j++) {
+    G::load(t, rec + (size_t) j * L);
+    G::mul(acc, acc, t);
+    v &= flags[j];
+  }
+  if (!v) G::one(acc);
+  G::store(gt, acc);
+}
+
 // Z_r arithmetic on element_to_bytes records: the F_q routines of fp.cuh on a constant block whose modulus is the group
 // order r (the reference runs its F_p back end on r: pairing->Zr).  op 0 mul, 1 add, 2 sub, 3 invert, 4 neg, 5 halve,
 // 6 double, 7 div (a / b), 8 element_from_hash (a: a digest of hlen bytes; fp_from_hash arith/montfp.c:440-448)

@@ -31,6 +31,7 @@
 using namespace pbc;
 
 #include "host_params.h"
+#include "ragged_plan.h"
 
 #define HIP_TRY(x)                                                                   \
   do {                                                                               \
@@ -166,7 +167,15 @@ bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb);
 void *workspace_get(pbc_hip_pairing_s *P, hipStream_t s, size_t bytes, int part = 0);   // part 1: the entry's second buffer (ProdWs::get2)
 void workspace_unpin(pbc_hip_pairing_s *P, hipStream_t s);
 // A workspace that belongs to one stream of a device context of the host-buffer path: grown on demand, freed with the context.
-struct OwnWs { void **p; size_t *cap; void **p2; size_t *cap2; };     // (p2 / cap2: the second buffer, ProdWs::get2)
+// Page-locked host staging that belongs to a workspace (ragged products: the plan of a call on its way to the device).
+// An asynchronous copy reads it after the call has returned, so the next call waits for THAT COPY -- not for the
+// kernels behind it -- before it writes: `ev` is recorded right behind the copy.
+struct HostStage { void *h = nullptr; size_t cap = 0; hipEvent_t ev = nullptr; bool pending = false; };
+void *stage_acquire(HostStage &st, size_t bytes);      // at least `bytes`, no copy in flight (grown on demand; null: fail() was called)
+int stage_copied(HostStage &st, hipStream_t s);        // call right after enqueueing the copy that reads the staging
+void stage_free(HostStage &st);
+struct OwnWs { void **p; size_t *cap; void **p2; size_t *cap2; HostStage *stage = nullptr; };     // (p2 / cap2: the second buffer, ProdWs::get2)
+HostStage *workspace_stage(pbc_hip_pairing_s *P, hipStream_t s);   // the staging of the PINNED table entry of (current device, s)
 void *own_workspace(const OwnWs &o, hipStream_t s, size_t bytes);
 void *object_scratch(pbc_hip_pairing_s *P, const void *key, size_t bytes, bool *fresh);    // small per-(device, key) buffers the object keeps (pbc_hip.hip)
 // The workspace of one product launch: the caller's own (host-buffer path) or the object's table entry for (device,
@@ -197,6 +206,8 @@ struct ProdWs {
     pinned = pinned || w != nullptr;
     return w;
   }
+  // the workspace's host staging (after get / get2: the table entry is pinned and its issue lock held)
+  HostStage *stage() { return own ? own->stage : (pinned ? workspace_stage(P, s) : nullptr); }
 };
 // The host-buffer path (pbc_hip.hip): chunks over the device set, page-locked buffers in place, anything else staged
 // through per-device chunk buffers that the object keeps.  `launch` enqueues one chunk (device pointers) on a stream.
@@ -206,6 +217,16 @@ int run_host_generic(pbc_hip_pairing_s *P, uint8_t *out, size_t ut, const uint8_
 // n single pairings on stream s through the launch path of element_pairing_batch (pbc_hip.hip launch_prod, k = 1: wave
 // routes and lane kernels are chosen there); constants already derived
 int launch_pairings(pbc_hip_pairing_s *P, void *d_gt, const void *d_g1, const void *d_g2, size_t n, hipStream_t s, const OwnWs *own);
+// Ragged products (pbc_hip_ragged.hip): n products on stream s, product u = terms offsets[u] - offsets[0] .. of the
+// device arrays (offsets: HOST memory, n + 1 values, checked by the caller; read before the call returns)
+int ragged_launch(pbc_hip_pairing_s *P, void *d_gt, const void *d_g1, const void *d_g2, const uint64_t *offsets, size_t n,
+                  hipStream_t s, const OwnWs *own);
+// ... over host buffers (pbc_hip.hip): contiguous ranges of products, balanced by terms, over the device set
+int run_host_ragged(pbc_hip_pairing_s *P, uint8_t *gt, const uint8_t *g1, const uint8_t *g2, const uint64_t *offsets, size_t n);
+// The record route of the 512-bit type a (pbc_hip_a.hip): Miller records of the T terms, folds, finish.  d_plan: the
+// level arrays on the device (each n + 1 values), sizes[i] = records of level i; recA / recB: room for sizes[0] / sizes[1] records
+int ragged_records_a(pbc_hip_pairing_s *P, void *d_gt, const void *d_g1, const void *d_g2, size_t n, unsigned F,
+                     const uint64_t *const *d_plan, const size_t *sizes, int nlevels, void *recA, void *recB, hipStream_t s);
 // Per-family launchers: k-term products (k = 1: single pairings) of n units on stream s; constants already derived.
 int launch_a(pbc_hip_pairing_s *P, void *d_gt, const void *d_g1, const void *d_g2, size_t n, int k, hipStream_t s, ProdWs &W);   // pbc_hip_a.hip: a, a1, e
 int launch_d(pbc_hip_pairing_s *P, void *d_gt, const void *d_g1, const void *d_g2, size_t n, int k, hipStream_t s, ProdWs &W);   // pbc_hip_d.hip: d, g

@@ -69,6 +69,7 @@ struct pbc_hip_pairing_s {
   bool group_slow;           // group operations: only the complete ladders ("hip_group_slow 1": tests, A/B)
   bool a_multi_compose;      // type a, pow2 / pow3 on G1 / G2: single-base ladders + additions instead of the joint ladder ("hip_multi_compose 1": A/B)
   int resident_slots;        // > 0: workgroups of a resident launch instead of the occupancy query ("hip_resident_slots N", tests)
+  int ragged_fold;           // ragged products: records a fold lane multiplies ("hip_ragged_fold N", 2..64; ragged_plan.h)
   size_t host_chunk;         // host-buffer entry points: units per chunk when the parameter text says "hip_host_chunk N" (0: default)
   size_t a_wave4_max;        // ... and up to this size four wavefronts per pairing ("hip_wave4_max N")
   size_t a_wave2_max;        // ... and between the two, up to this size, two ("hip_wave2_max N", round 5)

@@ -692,6 +692,57 @@ struct AL {
     final_exp(out);
     a_store_gt<N>(gt, out, valid);
   }
+
+  // ---- ragged products (pbc_hip_element_prod_pairing_ragged_batch) -------------------------------------------------
+  // One fold step of a product whose terms are spread over many lanes: the cnt >= 1 consecutive records of ONE product
+  // -> one record of the same format, its flag the AND of theirs.  A product of two P-class values is P-class again
+  // (fmul's lazy sums end in a reduction), so a folded record is what a Miller record is to the next level and to
+  // prod_finish_lane: one final exponentiation per product, however its terms were dealt out.
+  static PBC_DEV void fold_lane(uint4 *out, const uint4 *rec, int cnt) {
+    el x, y;
+    bool valid = record_get(x, y, rec);
+    lds_put(SLOT_FX, x);
+    lds_put(SLOT_FY, y);
+    for (int j = 1; j < cnt; j++) {
+      valid &= record_get(x, y, rec + (size_t) j * MREC);
+      fmul(x, y);
+    }
+    lds_get(x, SLOT_FX);
+    lds_get(y, SLOT_FY);
+    AL_HS(if (x.hs_u > U_STRICT || y.hs_u > U_STRICT || x.hs_B > 1.5 || y.hs_B > 1.5) hs_fail("folded value not P-class", x.hs_B);)
+    uint32_t w[4 * MREC];
+#pragma unroll
+    for (int i = 0; i < L; i++) { w[i] = x.l[i]; w[L + i] = y.l[i]; }
+#pragma unroll
+    for (int i = 2 * L; i < 4 * MREC; i++) w[i] = valid ? 1u : 0u;
+#pragma unroll
+    for (int i = 0; i < MREC; i++) out[i] = make_uint4(w[4 * i], w[4 * i + 1], w[4 * i + 2], w[4 * i + 3]);
+  }
+  // The all-zero G2 record is O to every entry point (include/pbc_hip.h, "zero-filled records"), but on y^2 = x^3 + x it
+  // is the finite point (0, 0), which miller_lane accepts: its pairing value is 1, so a single pairing is right, while a
+  // product that holds it has to be the identity whatever its other terms are.  The ragged route therefore clears the
+  // flag of such a term's record after the Miller kernel, which stays as it is.
+  static PBC_DEV void ragged_mask_lane(uint4 *rec, const uint8_t *g2) {
+    uint32_t any = 0;
+    for (int i = 0; i < 8 * N; i++) any |= g2[i];
+    if (any) return;
+    uint32_t *w = reinterpret_cast<uint32_t *>(rec);
+    for (int i = 2 * L; i < 4 * MREC; i++) w[i] = 0;
+  }
+  // prod_finish_lane with a count per product; cnt == 0 (rec: any readable record): the empty product, the identity
+  static PBC_DEV void ragged_finish_lane(uint8_t *gt, const uint4 *rec, int cnt) {
+    el x, y;
+    bool valid = record_get(x, y, rec);
+    lds_put(SLOT_FX, x);
+    lds_put(SLOT_FY, y);
+    for (int j = 1; j < cnt; j++) {
+      valid &= record_get(x, y, rec + (size_t) j * MREC);
+      fmul(x, y);
+    }
+    fp2<N> out;
+    final_exp(out);
+    a_store_gt<N>(gt, out, valid & (cnt > 0));
+  }
 };
 
 }  // namespace pbc

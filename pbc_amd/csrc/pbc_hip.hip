@@ -304,6 +304,10 @@ extern "C" int pbc_hip_pairing_init_set_buf(pbc_hip_pairing_t **out, const char 
     int gs = 0;                        // "hip_group_slow 1": element_mul_zn / GT pow_zn on the complete bit-by-bit ladders only
     pbc_host::param_int(param, len, "hip_group_slow", gs);
     P->group_slow = gs != 0;
+    int rf = pbc_host::kRaggedFoldDefault;   // "hip_ragged_fold N": records per fold lane of the ragged products (every value: the same bytes)
+    pbc_host::param_int(param, len, "hip_ragged_fold", rf);
+    if (rf < 2 || rf > 64) rc = fail("hip_ragged_fold must be 2..64 (got %d)", rf);
+    P->ragged_fold = rf;
     int mc = 0;                        // "hip_multi_compose 1": type a pow2 / pow3 as single-base ladders + additions (A/B with the joint ladder)
     pbc_host::param_int(param, len, "hip_multi_compose", mc);
     P->a_multi_compose = mc != 0;
@@ -549,6 +553,7 @@ struct DevCtx {
   size_t wscap[kSlots] = {0, 0, 0};
   void *ws2[kSlots] = {nullptr, nullptr, nullptr};                                         // ... and its second buffer (ProdWs::get2)
   size_t ws2cap[kSlots] = {0, 0, 0};
+  HostStage hs[kSlots];                                                                    // ... and its host staging (ProdWs::stage)
 };
 // Workspaces of the product kernels (per-term Miller state).  The host-buffer path owns one per stream of its device
 // contexts (DevCtx::ws: they live and die with the streams).  Launches of the *_dev entry points on CALLER streams get one
@@ -560,7 +565,7 @@ struct DevCtx {
 // launch on the same (object, stream) pair take turns, so the complete pass of a two-pass operation always reads the flags
 // its own fast pass wrote (the stream runs each call's kernels back to back).  Recursive: a call may ask twice.
 // p2 / cap2: the entry's second buffer (ProdWs::get2: intermediates a composed call keeps across a launcher's own request).
-struct WsEnt { int dev; hipStream_t st; void *p; size_t cap; uint64_t used; int pins; std::recursive_mutex issue; void *p2 = nullptr; size_t cap2 = 0; };
+struct WsEnt { int dev; hipStream_t st; void *p; size_t cap; uint64_t used; int pins; std::recursive_mutex issue; void *p2 = nullptr; size_t cap2 = 0; HostStage hs; };
 constexpr size_t kMaxWs = 8;
 // Small device buffers that belong to the object and a device, kept until the object is cleared: the schedule of the type d
 // wave kernel (read-only, shared by every launch), the wire-format staging area of the limb-image host calls.  Plain
@@ -576,6 +581,27 @@ struct HostCtx {
   uint64_t ws_clock = 0;
   std::mutex mu;                               // guards the tables (the per-device entries are used by one worker each)
 };
+void *stage_acquire(HostStage &st, size_t bytes) {
+  if (st.pending) { (void) hipEventSynchronize(st.ev); st.pending = false; }
+  if (st.cap < bytes) {
+    if (st.h) (void) hipHostFree(st.h);
+    st.h = nullptr; st.cap = 0;
+    if (hipHostMalloc(&st.h, bytes, hipHostMallocPortable) != hipSuccess) { st.h = nullptr; fail("hipHostMalloc(%zu) failed for a plan's staging", bytes); return nullptr; }
+    st.cap = bytes;
+  }
+  if (!st.ev && hipEventCreateWithFlags(&st.ev, hipEventDisableTiming) != hipSuccess) { st.ev = nullptr; fail("hipEventCreate failed"); return nullptr; }
+  return st.h;
+}
+int stage_copied(HostStage &st, hipStream_t s) {
+  HIP_TRY(hipEventRecord(st.ev, s));
+  st.pending = true;
+  return 0;
+}
+void stage_free(HostStage &st) {          // (the device the staging was used on is current and idle)
+  if (st.ev) (void) hipEventDestroy(st.ev);
+  if (st.h) (void) hipHostFree(st.h);
+  st = HostStage();
+}
 static void scratch_free_all(HostCtx *H) {
   for (ScratchEnt &x : H->scratch) {
     DeviceGuard guard(x.dev);
@@ -592,6 +618,7 @@ static void devctx_free_buffers(DevCtx &c) {   // the calling thread's current d
     if (c.dt[i]) (void) hipFree(c.dt[i]);
     if (c.ws[i]) (void) hipFree(c.ws[i]);
     if (c.ws2[i]) (void) hipFree(c.ws2[i]);
+    stage_free(c.hs[i]);
     c.d1[i] = c.d2[i] = c.dt[i] = c.ws[i] = c.ws2[i] = nullptr;
     c.cap1[i] = c.cap2[i] = c.capt[i] = c.wscap[i] = c.ws2cap[i] = 0;
   }
@@ -620,6 +647,7 @@ static void hostctx_free(pbc_hip_pairing_s *P) {
     (void) hipDeviceSynchronize();
     (void) hipFree(w->p);
     (void) hipFree(w->p2);
+    stage_free(w->hs);
   }
   scratch_free_all(H);
   for (int i = 0; i < H->n; i++) devctx_release(H->dc[i]);
@@ -650,6 +678,7 @@ void *workspace_get(pbc_hip_pairing_s *P, hipStream_t s, size_t bytes, int part)
             (void) hipDeviceSynchronize();
             if (H->ws[lru]->p) (void) hipFree(H->ws[lru]->p);
             if (H->ws[lru]->p2) (void) hipFree(H->ws[lru]->p2);
+            stage_free(H->ws[lru]->hs);
           }
           H->ws.erase(H->ws.begin() + (long) lru);
         }                                  // (every entry pinned: the table grows past kMaxWs for the moment)
@@ -689,6 +718,15 @@ void workspace_unpin(pbc_hip_pairing_s *P, hipStream_t s) {
   }
   if (e) e->issue.unlock();                // (the calling thread is the one that locked it: ProdWs is scoped to one call)
 }
+HostStage *workspace_stage(pbc_hip_pairing_s *P, hipStream_t s) {
+  int dev = -1;
+  HostCtx *H = static_cast<HostCtx *>(P->host_ctx);
+  if (!H || hipGetDevice(&dev) != hipSuccess) return nullptr;
+  std::lock_guard<std::mutex> lk(H->mu);
+  for (auto &w : H->ws)
+    if (w->dev == dev && w->st == s && w->pins > 0) return &w->hs;
+  return nullptr;
+}
 // at least `bytes` of device memory for (current device, key); *fresh = the buffer was (re)allocated: its old contents are gone
 void *object_scratch(pbc_hip_pairing_s *P, const void *key, size_t bytes, bool *fresh) {
   int dev = -1;
@@ -726,6 +764,7 @@ extern "C" int pbc_hip_pairing_release_workspaces(pbc_hip_pairing_t *P) {
     (void) hipDeviceSynchronize();
     if (w->p) (void) hipFree(w->p);
     if (w->p2) (void) hipFree(w->p2);
+    stage_free(w->hs);
   }
   H->ws.clear();
   scratch_free_all(H);
@@ -826,7 +865,7 @@ int run_host_generic(pbc_hip_pairing_s *P, uint8_t *gt, size_t ut, const uint8_t
     if (!c) return;
     size_t round = 0;
     if (zc) {                            // the kernels work on the caller's pinned buffers: no staging copies
-      const OwnWs own = {&c->ws[0], &c->wscap[0], &c->ws2[0], &c->ws2cap[0]};
+      const OwnWs own = {&c->ws[0], &c->wscap[0], &c->ws2[0], &c->ws2cap[0], &c->hs[0]};
       for (size_t idx = (size_t) d; idx < nchunks; idx += (size_t) ndev) {
         const size_t off = idx * chunk, m = n - off < chunk ? n - off : chunk;
         if (launch(zt + off * ut, z1 + off * u1, z2 ? z2 + off * u2 : nullptr, m, c->st[0], &own)) { *err = g_err; break; }
@@ -840,7 +879,7 @@ int run_host_generic(pbc_hip_pairing_s *P, uint8_t *gt, size_t ut, const uint8_t
       const size_t off = idx * chunk, m = n - off < chunk ? n - off : chunk;
       hipStream_t st = c->st[sl];
       if (!devctx_slot(c, sl, chunk * u1, g2 ? chunk * u2 : 0, chunk * ut, *err)) break;
-      const OwnWs own = {&c->ws[sl], &c->wscap[sl], &c->ws2[sl], &c->ws2cap[sl]};
+      const OwnWs own = {&c->ws[sl], &c->wscap[sl], &c->ws2[sl], &c->ws2cap[sl], &c->hs[sl]};
       if (hipMemcpyAsync(c->d1[sl], g1 + off * u1, m * u1, hipMemcpyHostToDevice, st) != hipSuccess ||
           (g2 && hipMemcpyAsync(c->d2[sl], g2 + off * u2, m * u2, hipMemcpyHostToDevice, st) != hipSuccess)) { *err = "H2D copy failed"; break; }
       if (launch(c->dt[sl], c->d1[sl], g2 ? c->d2[sl] : nullptr, m, st, &own)) { *err = g_err; break; }
@@ -869,6 +908,75 @@ static int run_host(pbc_hip_pairing_s *P, uint8_t *gt, const uint8_t *g1, const 
                           [P, k](void *d_gt, const void *d_g1, const void *d_g2, size_t m, hipStream_t s, const OwnWs *own) {
                             return launch_prod(P, d_gt, d_g1, d_g2, m, k, s, false, own);
                           }, true);
+}
+
+// Ragged products over host buffers (pbc_hip_element_prod_pairing_ragged_batch): units of different sizes, so the
+// batch is cut by TERMS -- one contiguous range of products per position of the device set, balanced by term count
+// (a device listed twice gets two), each range in chunks of about 2^20 terms that end at product boundaries (a longer
+// product is a chunk of its own) -- and always staged: H2D, ragged_launch, D2H on the ring of three streams per device,
+// through the chunk buffers, workspaces and plan staging the object keeps.  offsets: checked by the caller.
+int run_host_ragged(pbc_hip_pairing_s *P, uint8_t *gt, const uint8_t *g1, const uint8_t *g2, const uint64_t *offsets, size_t n) {
+  if (P->device < 0) return fail("no HIP device: libpbc_hip has no CPU fallback");
+  if (!n) return 0;
+  const size_t l1 = (size_t) P->len1, l2 = (size_t) P->len2, lt = (size_t) P->lenT;
+  const uint64_t T = offsets[n];
+  if (ranges_overlap(gt, n * lt, g1, T * l1) || ranges_overlap(gt, n * lt, g2, T * l2)) {
+    std::vector<uint8_t> tmp(n * lt);
+    if (run_host_ragged(P, tmp.data(), g1, g2, offsets, n)) return 1;
+    memcpy(gt, tmp.data(), tmp.size());
+    return 0;
+  }
+  const int ndev = P->ndev > 0 ? P->ndev : 1;
+  const int *devs = P->ndev > 0 ? P->devs : &P->device;
+  // range d: products first[d] .. first[d + 1], the first product at which the terms so far reach d T / ndev
+  size_t first[kMaxDev + 1];
+  first[0] = 0;
+  for (int d = 1; d <= ndev; d++) {
+    size_t u = first[d - 1];
+    if (d == ndev) u = n;
+    else while (u < n && offsets[u] * (uint64_t) ndev < T * (uint64_t) d) u++;
+    first[d] = u;
+  }
+  const uint64_t chunk_terms = P->host_chunk ? (uint64_t) P->host_chunk : (uint64_t) 1 << 20;
+  DeviceGuard guard(devs[0]);
+  if (!P->host_ctx) P->host_ctx = new HostCtx();
+  if (ensure_derived(P, 0)) return 1;
+  auto worker = [&](int d, std::string *err) {
+    if (first[d] == first[d + 1]) return;
+    if (hipSetDevice(devs[d]) != hipSuccess) { *err = "hipSetDevice failed"; return; }
+    DevCtx *c = devctx_get(P, d, devs[d], *err);
+    if (!c) return;
+    size_t round = 0;
+    for (size_t u0 = first[d]; u0 < first[d + 1]; round++) {
+      size_t u1 = u0 + 1;                // at least one product; more while the chunk stays within chunk_terms (and 2^20 products)
+      while (u1 < first[d + 1] && offsets[u1 + 1] - offsets[u0] <= chunk_terms && u1 - u0 < ((size_t) 1 << 20)) u1++;
+      const size_t m = u1 - u0, t0 = (size_t) offsets[u0], nt = (size_t) (offsets[u1] - offsets[u0]);
+      const int sl = (int) (round % kSlots);
+      hipStream_t st = c->st[sl];
+      if (!devctx_slot(c, sl, nt * l1, nt * l2, m * lt, *err)) break;
+      const OwnWs own = {&c->ws[sl], &c->wscap[sl], &c->ws2[sl], &c->ws2cap[sl], &c->hs[sl]};
+      if (nt && (hipMemcpyAsync(c->d1[sl], g1 + t0 * l1, nt * l1, hipMemcpyHostToDevice, st) != hipSuccess ||
+                 hipMemcpyAsync(c->d2[sl], g2 + t0 * l2, nt * l2, hipMemcpyHostToDevice, st) != hipSuccess)) { *err = "H2D copy failed"; break; }
+      if (ragged_launch(P, c->dt[sl], c->d1[sl], c->d2[sl], offsets + u0, m, st, &own)) { *err = g_err; break; }
+      if (hipMemcpyAsync(gt + u0 * lt, c->dt[sl], m * lt, hipMemcpyDeviceToHost, st) != hipSuccess) { *err = "D2H copy failed"; break; }
+      u0 = u1;
+    }
+    for (int i = 0; i < kSlots; i++) {
+      hipError_t e = hipStreamSynchronize(c->st[i]);
+      if (e != hipSuccess && err->empty()) *err = std::string("kernel failed: ") + hipGetErrorString(e);
+    }
+  };
+  std::string errs[kMaxDev];
+  if (ndev == 1) {
+    worker(0, &errs[0]);
+  } else {
+    std::thread th[kMaxDev];
+    for (int d = 0; d < ndev; d++) th[d] = std::thread(worker, d, &errs[d]);
+    for (int d = 0; d < ndev; d++) th[d].join();
+  }
+  for (int d = 0; d < ndev; d++)
+    if (!errs[d].empty()) return fail("device %d: %s", devs[d], errs[d].c_str());
+  return 0;
 }
 
 extern "C" int pbc_hip_host_alloc(void **out, size_t bytes) {

@@ -180,6 +180,63 @@ __global__ void __launch_bounds__(kBlock, PBC_A_WAVES) al_prod_finish_kernel(uin
   }
 }
 
+// Ragged products (pbc_hip_element_prod_pairing_ragged_batch) on the same records.  oin / oout: the plan's offset arrays
+// of this level and the next (n + 1 values each, ragged_plan.h).  Output record j belongs to the product u with
+// oout[u] <= j < oout[u + 1] -- found by binary search, empty products share an offset with their successor and are
+// never found -- and is the product of records oin[u] + b F .. of its block b = j - oout[u].
+static __device__ __forceinline__ size_t ragged_find(const uint64_t *o, size_t n, uint64_t j) {
+  size_t lo = 0, hi = n;                 // the first index in (0, n] whose offset exceeds j, minus one
+  while (lo < hi) {
+    const size_t mid = (lo + hi) >> 1;
+    if (o[mid + 1] > j) hi = mid; else lo = mid + 1;
+  }
+  return lo;
+}
+// one term per lane: the record of a term whose G2 record is all zero loses its flag (pairing_al.cuh ragged_mask_lane)
+template <int N>
+__global__ void __launch_bounds__(kBlock) al_ragged_mask_kernel(uint4 *ws, const uint8_t *g2, size_t n) {
+  size_t idx = (size_t) blockIdx.x * kBlock + threadIdx.x;
+  if (idx >= n) return;
+  AL<N>::ragged_mask_lane(ws + idx * AL<N>::MREC, g2 + idx * 8 * N);
+}
+template <int N>
+__global__ void __launch_bounds__(kBlock, PBC_A_WAVES) al_ragged_fold_kernel(uint4 *out, const uint4 *in, const uint64_t *oin, const uint64_t *oout,
+                                                                             size_t n, size_t nout, unsigned F, unsigned *ctr, KArgs<N> ka) {
+  PBC_RESIDENT_LOOP(nout, ctr) {
+    size_t idx = PBC_UNIT_INDEX;
+    size_t ld = idx < nout ? idx : nout - 1;
+    const size_t u = ragged_find(oout, n, ld);
+    const uint64_t start = oin[u] + (ld - oout[u]) * F, left = oin[u + 1] - start;
+    const int cnt = (int) (left < F ? left : F);
+    uint4 rec[AL<N>::MREC];
+    AL<N>::fold_lane(rec, in + start * AL<N>::MREC, cnt);
+    if (idx < nout) {
+#pragma unroll
+      for (int i = 0; i < AL<N>::MREC; i++) out[idx * AL<N>::MREC + i] = rec[i];
+    }
+  }
+}
+// one product per lane: its last records (at most F; none: the identity) -> GT bytes.  nrec >= 1 records are readable.
+template <int N>
+__global__ void __launch_bounds__(kBlock, PBC_A_WAVES) al_ragged_finish_kernel(uint8_t *gt, const uint4 *ws, const uint64_t *off, size_t n, size_t nrec,
+                                                                               unsigned *ctr, KArgs<N> ka) {
+  PBC_RESIDENT_LOOP(n, ctr) {
+    size_t idx = PBC_UNIT_INDEX;
+    size_t ld = idx < n ? idx : n - 1;
+    constexpr int L = 8 * N;
+    __attribute__((aligned(16))) uint8_t out[L];
+    const uint64_t a = off[ld], b = off[ld + 1];
+    const size_t at = a < nrec ? (size_t) a : nrec - 1;        // (an empty product reads a record it does not use)
+    AL<N>::ragged_finish_lane(out, ws + at * AL<N>::MREC, (int) (b - a));
+    if (idx < n) {
+      uint4 *dst = reinterpret_cast<uint4 *>(gt + idx * L);
+      const uint4 *src = reinterpret_cast<const uint4 *>(out);
+#pragma unroll
+      for (int i = 0; i < L / 16; i++) dst[i] = src[i];
+    }
+  }
+}
+
 // One k-term product of Type-A pairings per lane (terms of unit u are records u*k .. u*k+k-1).  `ws` is the object's
 // workspace for the per-term Miller state: k x 24 x 128 uint4 per workgroup (a_prod_pairing_lane).
 template <int N>
@@ -317,6 +374,32 @@ int derive_e(pbc_hip_pairing_s *P, hipStream_t s) {
   HIP_TRY(hipGetLastError());
   if (P->econst.rxs < 1 || P->econst.rxs > 255)      // the steps multiply by x_R with additions (pairing_e.cuh)
     return fail("type e: no auxiliary point with x in 1..255 on this curve (found x = %d)", P->econst.rxs);
+  return 0;
+}
+
+// The record route of a ragged call (host_common.h): al_miller_kernel over every term, one fold kernel per level of the
+// plan (records ping-pong between recA and recB), one final exponentiation per product in the finish kernel.
+int ragged_records_a(pbc_hip_pairing_s *P, void *d_gt, const void *d_g1, const void *d_g2, size_t n, unsigned F,
+                     const uint64_t *const *d_plan, const size_t *sizes, int nlevels, void *recA, void *recB, hipStream_t s) {
+  uint4 *cur = (uint4 *) recA, *nxt = (uint4 *) recB;
+  const size_t T = sizes[0];
+  if (T) {
+    hipLaunchKernelGGL(al_miller_kernel<16>, dim3(resident_grid(P, reinterpret_cast<const void *>(&al_miller_kernel<16>), T)), dim3(kBlock), 0, s,
+                       cur, (const uint8_t *) d_g1, (const uint8_t *) d_g2, T, unit_counter(P, s), kargs<16>(P));
+    hipLaunchKernelGGL(al_ragged_mask_kernel<16>, dim3((unsigned) ((T + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, cur, (const uint8_t *) d_g2, T);
+  } else {
+    HIP_TRY(hipMemsetAsync(cur, 0, AL<16>::MREC * sizeof(uint4), s));     // every product is empty: one record the finish lanes may read
+  }
+  for (int l = 0; l + 1 < nlevels; l++) {
+    const size_t nout = sizes[l + 1];
+    hipLaunchKernelGGL(al_ragged_fold_kernel<16>, dim3(resident_grid(P, reinterpret_cast<const void *>(&al_ragged_fold_kernel<16>), nout)), dim3(kBlock), 0, s,
+                       nxt, (const uint4 *) cur, d_plan[l], d_plan[l + 1], n, nout, F, unit_counter(P, s), kargs<16>(P));
+    std::swap(cur, nxt);
+  }
+  const size_t nrec = sizes[nlevels - 1] ? sizes[nlevels - 1] : 1;
+  hipLaunchKernelGGL(al_ragged_finish_kernel<16>, dim3(resident_grid(P, reinterpret_cast<const void *>(&al_ragged_finish_kernel<16>), n)), dim3(kBlock), 0, s,
+                     (uint8_t *) d_gt, (const uint4 *) cur, d_plan[nlevels - 1], n, nrec, unit_counter(P, s), kargs<16>(P));
+  HIP_TRY(hipGetLastError());
   return 0;
 }
 
