@@ -231,6 +231,64 @@ void pbc_hip_pairing_pp_clear(pbc_hip_pp_t *pp);
 int pbc_hip_pairing_pp_apply_batch(pbc_hip_pp_t *pp, uint8_t *gt, const uint8_t *g2, size_t n);
 int pbc_hip_pairing_pp_apply_batch_dev(pbc_hip_pp_t *pp, void *d_gt, const void *d_g2, size_t n, void *stream);
 
+/* Table sets: MANY fixed first arguments in one object -- a validator set of public keys, each checking
+ * e(pk_t, H(m)) for its own messages (the second pairing of example/bls.c:70-78 on the symmetric types); the few key
+ * components that are the first arguments of every product of an ABE decryption or a Groth16-style verification.
+ * A set holds m tables of pairing_pp_init (include/pbc_pairing.h:54-89 -> a_pairing_pp_init ecc/a_param.c:149-220, its
+ * a1 pair ecc/a_param.c:1632-1818, the pairs of types d and g ecc/d_param.c:794-966, ecc/g_param.c:619-787) in ONE
+ * device allocation, table after table, with one flag word per table and a copy of the m G1 records; ONE kernel launch
+ * builds them, one first argument per lane.  Table t holds exactly the words pbc_hip_pairing_pp_init derives from g1[t].
+ * Families: those of pbc_hip_pairing_pp_init -- type a (512-bit q and the generic sizes), a1, d, g; types e and f are
+ * refused with its message.  The set lives on the device the pairing object was created on, as pbc_hip_element_pp_t does.
+ *   _init      g1: m records in HOST memory; returns when the tables are built.
+ *   _init_dev  d_g1: m records in device memory; copy and kernel are enqueued on `stream`, asynchronous -- the set may be
+ *              used on that stream at once, on another one after the caller has ordered the two.
+ * Errors (non-zero; checked before the device is looked for, so they are reported without one): null arguments, m == 0,
+ * a type e / f object, m tables overflowing size_t.  _clear frees the set (it waits for kernels that still read it). */
+typedef struct pbc_hip_pp_set_s pbc_hip_pp_set_t;
+int pbc_hip_pairing_pp_set_init(pbc_hip_pp_set_t **set, pbc_hip_pairing_t *p, const uint8_t *g1, size_t m);
+int pbc_hip_pairing_pp_set_init_dev(pbc_hip_pp_set_t **set, pbc_hip_pairing_t *p, const void *d_g1, size_t m, void *stream);
+void pbc_hip_pairing_pp_set_clear(pbc_hip_pp_set_t *set);
+size_t pbc_hip_pairing_pp_set_count(const pbc_hip_pp_set_t *set);
+/* Segmented pairing_pp_apply (a_pairing_pp_apply ecc/a_param.c:317-360, a1_pairing_pp_apply ecc/a_param.c:1728-1818,
+ * d_pairing_pp_apply ecc/d_param.c:908-966, ecc/g_param.c:741-787): table t serves its own range of second arguments,
+ *     gt[i] = to_bytes( e(g1[t], g2[i]) ),   offsets[t] <= i < offsets[t+1],   t < m,
+ * in one launch.  offsets: m + 1 values in HOST memory in both forms, offsets[0] == 0, non-decreasing; n = offsets[m] is
+ * the number of records in g2 / gt; a table may serve no unit; n == 0 returns 0.  The array is read before the call
+ * returns -- also by the asynchronous _dev form.  The bytes are those of pbc_hip_pairing_pp_apply_batch on table t, i.e.
+ * of element_pairing; the identity when g1[t] or g2[i] deserialises to O.
+ * The apply lanes read their table as wave-uniform data, so the host deals the units out to wave slots -- one descriptor
+ * (table, first unit, count <= 64) per wavefront, ceil(c / 64) for a table of c units -- and uploads that plan in
+ * stream order from page-locked staging into the second buffer of the (device, stream) workspace (24 bytes per slot;
+ * see the ragged products above: calls enqueued back to back on one stream with different offsets are independent).
+ * Lanes of a slot beyond its count repeat its last unit and store nothing.  Every batch size runs on the lane kernels.
+ * Host-buffer form: staged through the object's chunk buffers on the set's device (a device set is not used).
+ * Errors, checked before the device: null arguments, offsets[0] != 0, a decreasing pair of offsets. */
+int pbc_hip_pairing_pp_set_apply_batch(pbc_hip_pp_set_t *set, uint8_t *gt, const uint8_t *g2, const uint64_t *offsets);
+int pbc_hip_pairing_pp_set_apply_batch_dev(pbc_hip_pp_set_t *set, void *d_gt, const void *d_g2,
+                                           const uint64_t *offsets /* HOST memory */, void *stream);
+/* The wave plan of such a call (pure host code, no device; the tests' view of the planner): three values per slot --
+ * table, first unit, count -- in slot order.  Returns the number of values (at most `cap` are written to out, which may
+ * be null); 0 for offsets the entry points refuse. */
+size_t pbc_hip_diag_pp_set_plan(pbc_hip_pairing_t *p, const uint64_t *offsets, size_t m, uint64_t *out, size_t cap);
+/* Products whose first arguments are the set's, the same m for every product (element_prod_pairing,
+ * include/pbc_pairing.h:153-171, with preprocessed first arguments):
+ *     gt[u] = to_bytes( prod_{j<m} e(g1[j], g2[u*m + j]) ),   u < n.
+ * Semantics and bytes are those of pbc_hip_element_prod_pairing_batch on the same terms with the m first arguments
+ * repeated for every product: a g1[j] that deserialises to O makes EVERY product the identity, a g2 term that does makes
+ * ITS product the identity (include/pbc_pairing.h:161-168).  Inherited as it stands on type a with a 512-bit q: the
+ * all-zero G2 record is the finite point (0, 0), whose pairing value 1 the uniform entry point multiplies into the
+ * product -- so does this one (the other families read the term with the loader of the group operations, to which the
+ * all-zero record is O, as the ragged call does).
+ * The terms run term-major on the plan above with an index stride: the wave slots of table j cover u = 0 .. n - 1, a
+ * lane reads g2[u*m + j].  Type a with a 512-bit q: 7 F_q products a Miller step instead of 18 and no point arithmetic,
+ * a 160-byte Miller record per term, then ONE final exponentiation per product; calls of more than 2^22 terms are cut
+ * into launch groups of whole products.  Every other family: the segmented apply into GT records, a validity byte per
+ * term, then the folds of the ragged products -- one final exponentiation per TERM.  Workspace: the
+ * second buffer of the (device, stream) entry -- plan, term records, fold levels.  n == 0 returns 0. */
+int pbc_hip_pairing_pp_set_prod_batch(pbc_hip_pp_set_t *set, uint8_t *gt, const uint8_t *g2, size_t n);
+int pbc_hip_pairing_pp_set_prod_batch_dev(pbc_hip_pp_set_t *set, void *d_gt, const void *d_g2, size_t n, void *stream);
+
 /* Batched group operations next to the pairing (the callers' other hot loops: example/bls.c
  * signs with element_pow_zn and checks with GT products).  Scalars are Z_r elements in
  * element_to_bytes form: big-endian, pbc_hip_pairing_length_in_bytes_Zr() bytes

@@ -136,6 +136,18 @@ def lib():
         L.pbc_hip_element_prod_pairing_ragged_batch_dev.argtypes = [vp, vp, vp, vp, vp, sz, vp]
         L.pbc_hip_diag_ragged_plan.restype = sz
         L.pbc_hip_diag_ragged_plan.argtypes = [vp, vp, sz, vp, sz]
+        L.pbc_hip_pairing_pp_set_init.argtypes = [ctypes.POINTER(vp), vp, vp, sz]
+        L.pbc_hip_pairing_pp_set_init_dev.argtypes = [ctypes.POINTER(vp), vp, vp, sz, vp]
+        L.pbc_hip_pairing_pp_set_clear.argtypes = [vp]
+        L.pbc_hip_pairing_pp_set_clear.restype = None
+        L.pbc_hip_pairing_pp_set_count.argtypes = [vp]
+        L.pbc_hip_pairing_pp_set_count.restype = sz
+        L.pbc_hip_pairing_pp_set_apply_batch.argtypes = [vp, vp, vp, vp]
+        L.pbc_hip_pairing_pp_set_apply_batch_dev.argtypes = [vp, vp, vp, vp, vp]
+        L.pbc_hip_diag_pp_set_plan.restype = sz
+        L.pbc_hip_diag_pp_set_plan.argtypes = [vp, vp, sz, vp, sz]
+        L.pbc_hip_pairing_pp_set_prod_batch.argtypes = [vp, vp, vp, sz]
+        L.pbc_hip_pairing_pp_set_prod_batch_dev.argtypes = [vp, vp, vp, sz, vp]
         _lib = L
     return _lib
 
@@ -171,6 +183,9 @@ EXPORTS = (
     "pbc_hip_element_prod_pairing_batch_limbs_dev",
     "pbc_hip_is_almost_coddh_batch", "pbc_hip_is_almost_coddh_batch_dev",
     "pbc_hip_element_prod_pairing_ragged_batch", "pbc_hip_element_prod_pairing_ragged_batch_dev", "pbc_hip_diag_ragged_plan",
+    "pbc_hip_pairing_pp_set_init", "pbc_hip_pairing_pp_set_init_dev", "pbc_hip_pairing_pp_set_clear", "pbc_hip_pairing_pp_set_count",
+    "pbc_hip_pairing_pp_set_apply_batch", "pbc_hip_pairing_pp_set_apply_batch_dev", "pbc_hip_diag_pp_set_plan",
+    "pbc_hip_pairing_pp_set_prod_batch", "pbc_hip_pairing_pp_set_prod_batch_dev",
 )
 
 
@@ -659,6 +674,14 @@ class Pairing:
         """Mirror of pairing_pp_init: returns a PairingPP bound to the fixed first argument."""
         return PairingPP(self, g1)
 
+    def pp_set_init(self, g1):
+        """A table set: one pairing_pp table per row of ``g1`` (m, length_in_bytes_G1), built in one launch."""
+        return PairingPPSet(self, g1=g1)
+
+    def pp_set_init_dev(self, d_g1, m, stream=0):
+        """The same from m device-resident records, enqueued on ``stream`` (asynchronous)."""
+        return PairingPPSet(self, d_g1=d_g1, m=m, stream=stream)
+
     # ---- diagnostics ------------------------------------------------------------------
     def fq_op(self, op, a, b=None):
         import numpy as np
@@ -711,6 +734,91 @@ class PairingPP:
     def clear(self):
         if getattr(self, "_h", None):
             lib().pbc_hip_pairing_pp_clear(self._h)
+            self._h = None
+
+    __del__ = clear
+
+
+class PairingPPSet:
+    """m pairing_pp tables of one pairing object (include/pbc_hip.h pbc_hip_pp_set_t): a segmented pairing_pp_apply, and
+    products whose first arguments are the set's."""
+
+    def __init__(self, pairing, g1=None, d_g1=None, m=None, stream=0):
+        import numpy as np
+        self.pairing = pairing
+        self._h = ctypes.c_void_p()
+        if g1 is not None:
+            g1 = np.ascontiguousarray(g1, dtype=np.uint8)
+            if g1.size % pairing.length_in_bytes_G1:
+                raise ValueError("g1 must hold whole G1 records")
+            rc = lib().pbc_hip_pairing_pp_set_init(ctypes.byref(self._h), pairing._h, _np_ptr(g1) if g1.size else 1,
+                                                   g1.size // pairing.length_in_bytes_G1)
+        else:
+            rc = lib().pbc_hip_pairing_pp_set_init_dev(ctypes.byref(self._h), pairing._h, d_g1, m, stream)
+        if rc:
+            self._h = None
+            raise PbcHipError("pairing_pp_set_init: " + _err())
+        self.m = lib().pbc_hip_pairing_pp_set_count(self._h)
+
+    def _offsets(self, offsets):
+        import numpy as np
+        off = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
+        if off.size != self.m + 1:
+            raise ValueError("offsets needs m + 1 = %d values" % (self.m + 1))
+        return off
+
+    def apply(self, g2, offsets):
+        """gt[i] = e(g1[t], g2[i]) for offsets[t] <= i < offsets[t+1]: np.uint8 of shape (offsets[-1], length_in_bytes_GT)"""
+        import numpy as np
+        g2 = np.ascontiguousarray(g2, dtype=np.uint8)
+        off = self._offsets(offsets)
+        n = int(off[-1])
+        if g2.size != n * self.pairing.length_in_bytes_G2:
+            raise ValueError("g2 does not hold offsets[-1] = %d records" % n)
+        gt = np.empty((n, self.pairing.length_in_bytes_GT), np.uint8)
+        # (empty arrays still hand the library a non-null pointer)
+        if lib().pbc_hip_pairing_pp_set_apply_batch(self._h, _np_ptr(gt) if n else 1, _np_ptr(g2) if n else 1, _np_ptr(off)):
+            raise PbcHipError("pairing_pp_set_apply: " + _err())
+        return gt
+
+    def apply_dev(self, d_gt, d_g2, offsets, stream=0):
+        """the same on device pointers, enqueued on ``stream``; ``offsets`` is a host array and may be reused on return"""
+        off = self._offsets(offsets)
+        if lib().pbc_hip_pairing_pp_set_apply_batch_dev(self._h, d_gt, d_g2, _np_ptr(off), stream):
+            raise PbcHipError("pairing_pp_set_apply_dev: " + _err())
+
+    def prod(self, g2):
+        """gt[u] = prod over j < m of e(g1[j], g2[u*m + j]); g2 holds n*m records"""
+        import numpy as np
+        g2 = np.ascontiguousarray(g2, dtype=np.uint8)
+        per = self.m * self.pairing.length_in_bytes_G2
+        if g2.size % per:
+            raise ValueError("g2 must hold n * m records")
+        n = g2.size // per
+        gt = np.empty((n, self.pairing.length_in_bytes_GT), np.uint8)
+        if lib().pbc_hip_pairing_pp_set_prod_batch(self._h, _np_ptr(gt) if n else 1, _np_ptr(g2) if n else 1, n):
+            raise PbcHipError("pairing_pp_set_prod: " + _err())
+        return gt
+
+    def prod_dev(self, d_gt, d_g2, n, stream=0):
+        if lib().pbc_hip_pairing_pp_set_prod_batch_dev(self._h, d_gt, d_g2, n, stream):
+            raise PbcHipError("pairing_pp_set_prod_dev: " + _err())
+
+    def plan(self, offsets):
+        """the wave slots of a segmented apply (pbc_hip_diag_pp_set_plan): np.uint64 of shape (slots, 3) -- table, first unit, count"""
+        import numpy as np
+        off = self._offsets(offsets)
+        need = lib().pbc_hip_diag_pp_set_plan(self.pairing._h, _np_ptr(off), self.m, None, 0)
+        if not need and (off[0] != 0 or (np.diff(off.astype(np.int64)) < 0).any()):
+            raise PbcHipError("pp_set plan: offsets refused")
+        out = np.zeros(need, np.uint64)
+        if need:
+            lib().pbc_hip_diag_pp_set_plan(self.pairing._h, _np_ptr(off), self.m, _np_ptr(out), need)
+        return out.reshape(-1, 3)
+
+    def clear(self):
+        if getattr(self, "_h", None):
+            lib().pbc_hip_pairing_pp_set_clear(self._h)
             self._h = None
 
     __del__ = clear

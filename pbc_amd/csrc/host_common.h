@@ -32,6 +32,7 @@ using namespace pbc;
 
 #include "host_params.h"
 #include "ragged_plan.h"
+#include "pp_set_plan.h"
 
 #define HIP_TRY(x)                                                                   \
   do {                                                                               \
@@ -92,6 +93,32 @@ static __device__ __forceinline__ size_t pbc_unit_block(unsigned *ctr, size_t it
 }
 #define PBC_RESIDENT_LOOP(n, ctr) for (size_t it_ = 0, nvb_ = ((n) + 63) / 64, vb = pbc_unit_block(ctr, 0); vb < nvb_; vb = pbc_unit_block(ctr, ++it_))
 #define PBC_UNIT_INDEX (vb * 64 + (threadIdx.x & 63))
+// One wave slot of a table-set plan (pp_set_plan.h; the kernels *_pp_set_*): descriptor `slot` of `plan`, every field
+// made wave-uniform, so that the table pointer derived from it stays in scalar registers (the apply lanes convert the
+// table's words on the scalar unit).  rec(): the record a lane works on -- lanes at or beyond `count` are clamped to the
+// slot's last unit and store nothing, the `ld` clamp of the other kernels.  stride / tmul: 1 / 0 for a segmented apply
+// (unit i is record i); m / 1 for a product over the set (unit u of table j is term record u m + j).
+struct PpSlot {
+  size_t table, first;
+  unsigned count;
+  __device__ __forceinline__ bool live() const { return (threadIdx.x & 63) < count; }
+  __device__ __forceinline__ size_t rec(size_t stride, size_t tmul) const {
+    const unsigned lane = threadIdx.x & 63;
+    return (first + (lane < count ? lane : count - 1)) * stride + table * tmul;
+  }
+};
+static __device__ __forceinline__ uint64_t pbc_uniform64(uint64_t v) {
+  const uint32_t lo = (uint32_t) __builtin_amdgcn_readfirstlane((int) (uint32_t) v), hi = (uint32_t) __builtin_amdgcn_readfirstlane((int) (uint32_t) (v >> 32));
+  return ((uint64_t) hi << 32) | lo;
+}
+static __device__ __forceinline__ PpSlot pp_set_slot(const uint64_t *__restrict__ plan, size_t slot) {
+  const uint64_t *d = plan + slot * pbc_host::kPpSetSlotWords;
+  PpSlot s;
+  s.table = (size_t) pbc_uniform64(d[0]);
+  s.first = (size_t) pbc_uniform64(d[1]);
+  s.count = (unsigned) pbc_uniform64(d[2]);
+  return s;
+}
 static_assert(kBlock == D_LANES, "pairing_d.cuh sizes its LDS state for 128-lane workgroups");
 #ifndef PBC_DF_WAVES
 #define PBC_DF_WAVES 2
@@ -245,6 +272,37 @@ void pp_init_launch_a(pbc_hip_pairing_s *P, pbc_hip_pp_s *pp, const uint8_t *d_g
 int pp_init_launch_d(pbc_hip_pairing_s *P, pbc_hip_pp_s *pp, const uint8_t *d_g1);
 int pp_apply_launch_a(pbc_hip_pp_s *pp, void *d_gt, const void *d_g2, size_t n, hipStream_t s);
 int pp_apply_launch_d(pbc_hip_pp_s *pp, void *d_gt, const void *d_g2, size_t n, hipStream_t s);
+// Table sets (pbc_hip_ppset.hip; include/pbc_hip.h pbc_hip_pp_set_t): m tables of pairing_pp_init in ONE allocation,
+// table after table (table t: tabs + t tab_words, the layout pp_init_launch_* write), then one flag word per table and a
+// copy of the m G1 records.
+struct pbc_hip_pp_set_s {
+  pbc_hip_pairing_s *P;
+  int device;
+  size_t m, tab_words;
+  void *mem;          // the allocation
+  uint32_t *tabs;     // device: [m][tab_words]
+  uint32_t *flags;    // device: [m], first argument t was a finite curve point
+  uint8_t *g1;        // device: [m] G1 records
+};
+// one lane per first argument: every table and flag of the set, one launch on s
+int pp_set_init_launch_a(pbc_hip_pairing_s *P, pbc_hip_pp_set_s *set, bool a1, hipStream_t s);
+int pp_set_init_launch_d(pbc_hip_pairing_s *P, pbc_hip_pp_set_s *set, hipStream_t s);
+// The wave slots of a device-resident plan on the lane kernels: slot -> (table, units), lane -> record rec = (first +
+// lane) stride + table tmul of d_g2, GT record rec of d_out (PpSlot above)
+int pp_set_apply_launch_a(pbc_hip_pp_set_s *set, void *d_out, const void *d_g2, const uint64_t *d_plan, size_t slots, size_t stride, size_t tmul, hipStream_t s);
+int pp_set_apply_launch_d(pbc_hip_pp_set_s *set, void *d_out, const void *d_g2, const uint64_t *d_plan, size_t slots, size_t stride, size_t tmul, hipStream_t s);
+// The record route of a product over a set (512-bit type a): the plan's slots (term-major, pp_set_prod_plan) leave the
+// Miller record of term u m + j in recs, then al_prod_finish_kernel multiplies the m records of each of the n products
+int pp_set_records_a(pbc_hip_pp_set_s *set, void *d_gt, const void *d_g2, const uint64_t *d_plan, size_t slots, size_t n, void *recs, hipStream_t s);
+// The folds of the GT route of a ragged call (pbc_hip_ragged.hip) on records that are already in place: cur / fcur hold
+// sizes[0] GT records and their flag bytes, nxt / fnxt have room for sizes[1]; d_plan: the level arrays on the device
+int ragged_gt_reduce(pbc_hip_pairing_s *P, void *d_gt, void *cur, void *fcur, void *nxt, void *fnxt, const uint64_t *const *d_plan,
+                     const size_t *sizes, int nlevels, size_t n, unsigned F, hipStream_t s);
+// A host-buffer call that runs on the object's OWN device only (a table set lives there): n units of ui bytes in and uo
+// bytes out, staged in chunks of `chunk` units through the chunk buffers, streams and workspaces of that device's
+// context; `launch` enqueues the units c0 .. c0 + cnt of a chunk (device pointers to the chunk's first records)
+typedef std::function<int(void *d_out, const void *d_in, size_t c0, size_t cnt, hipStream_t s, const OwnWs *own)> RangeLaunch;
+int run_host_own_device(pbc_hip_pairing_s *P, uint8_t *out, size_t uo, const uint8_t *in, size_t ui, size_t n, size_t chunk, const RangeLaunch &launch);
 // type f diagnostics (pbc_hip_diag_stage)
 int diag_f_miller(pbc_hip_pairing_s *P, void *dt, const void *d1, const void *d2, size_t n);
 int diag_f_op(pbc_hip_pairing_s *P, int stage, void *dt, const void *d1, const void *d2, size_t n);

@@ -547,9 +547,10 @@ struct AL {
     mul(ly, Qy, c);
     fmul(lx, ly);
   }
-  // pairing_pp_apply for one lane (the table is the word-form one a_pp_init_lane writes, pairing_a.cuh).  Q stays in
-  // registers here: nothing else competes for them.
-  static PBC_DEV void pp_apply_lane(uint8_t *gt, const uint32_t *tab, bool p_valid, const uint8_t *g2) {
+  // The Miller loop of pairing_pp_apply for one lane (the table is the word-form one a_pp_init_lane writes,
+  // pairing_a.cuh): f ends up in its LDS slots, as after miller_lane; the return value is the pair's validity.  Q stays
+  // in registers here: nothing else competes for them.
+  static PBC_DEV bool pp_miller_lane(const uint32_t *tab, bool p_valid, const uint8_t *g2) {
     constexpr int NB = 4 * N;
     el Qx, Qy;
     bool valid;
@@ -575,6 +576,11 @@ struct AL {
       pp_line(tab, slot, Qx, Qy);
       if (i == c_a.exp1) pp_line(tab, c_a.exp2, Qx, Qy);
     }
+    return valid;
+  }
+  // pairing_pp_apply for one lane
+  static PBC_DEV void pp_apply_lane(uint8_t *gt, const uint32_t *tab, bool p_valid, const uint8_t *g2) {
+    const bool valid = pp_miller_lane(tab, p_valid, g2);
     fp2<N> out;
     final_exp(out);
     a_store_gt<N>(gt, out, valid);
@@ -652,7 +658,16 @@ struct AL {
   // by which the Miller values differ from the reference's die there).
   static constexpr int MREC = (2 * L + 1 + 3) / 4;        // uint4s per record: fx, fy (L limbs each), flag
   static PBC_DEV void miller_record_lane(uint4 *rec, const uint8_t *g1, const uint8_t *g2) {
-    const bool valid = miller_lane(g1, g2);
+    record_put(rec, miller_lane(g1, g2));
+  }
+  // The same record from a preprocessed first argument (products over a table set, pbc_hip_pairing_pp_set_prod_batch):
+  // pp_apply_lane's loop -- fsqr + pp_line, 7 F_q products a step instead of 18 -- and no final exponentiation.  The
+  // table's lines are those of miller_lane up to factors in F_q^*, which die in prod_finish_lane's exponentiation.
+  static PBC_DEV void pp_miller_record_lane(uint4 *rec, const uint32_t *tab, bool p_valid, const uint8_t *g2) {
+    record_put(rec, pp_miller_lane(tab, p_valid, g2));
+  }
+  // f of a finished Miller loop (its LDS slots) and the pair's validity -> a record
+  static PBC_DEV void record_put(uint4 *rec, bool valid) {
     el fx, fy;
     lds_get(fx, SLOT_FX);
     lds_get(fy, SLOT_FY);

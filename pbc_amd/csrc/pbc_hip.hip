@@ -979,6 +979,52 @@ int run_host_ragged(pbc_hip_pairing_s *P, uint8_t *gt, const uint8_t *g1, const 
   return 0;
 }
 
+// A host-buffer call on the object's OWN device only (host_common.h: the calls on a table set, whose tables live there --
+// a device set stays as it is for the other entry points): always staged, H2D -> launch -> D2H per chunk on the ring of
+// three streams of that device's context.  The context is the one of the device's position in the device set (position
+// 0 without a set), or the last position when the set does not name the device.
+int run_host_own_device(pbc_hip_pairing_s *P, uint8_t *out, size_t uo, const uint8_t *in, size_t ui, size_t n, size_t chunk, const RangeLaunch &launch) {
+  if (P->device < 0) return fail("no HIP device: libpbc_hip has no CPU fallback");
+  if (!n) return 0;
+  if (ranges_overlap(out, n * uo, in, n * ui)) {
+    std::vector<uint8_t> tmp(n * uo);
+    if (run_host_own_device(P, tmp.data(), uo, in, ui, n, chunk, launch)) return 1;
+    memcpy(out, tmp.data(), tmp.size());
+    return 0;
+  }
+  if (chunk < 1) chunk = 1;
+  if (chunk > n) chunk = n;
+  DeviceGuard guard(P->device);
+  if (!P->host_ctx) P->host_ctx = new HostCtx();
+  if (ensure_derived(P, 0)) return 1;
+  int slot = 0;
+  if (P->ndev > 0) {
+    slot = kMaxDev - 1;
+    for (int d = P->ndev - 1; d >= 0; d--) if (P->devs[d] == P->device) slot = d;
+  }
+  std::string err;
+  DevCtx *c = devctx_get(P, slot, P->device, err);
+  if (c) {
+    size_t round = 0;
+    for (size_t c0 = 0; c0 < n; c0 += chunk, round++) {
+      const int sl = (int) (round % kSlots);
+      const size_t cnt = n - c0 < chunk ? n - c0 : chunk;
+      hipStream_t st = c->st[sl];
+      if (!devctx_slot(c, sl, 0, chunk * ui, chunk * uo, err)) break;
+      const OwnWs own = {&c->ws[sl], &c->wscap[sl], &c->ws2[sl], &c->ws2cap[sl], &c->hs[sl]};
+      if (hipMemcpyAsync(c->d2[sl], in + c0 * ui, cnt * ui, hipMemcpyHostToDevice, st) != hipSuccess) { err = "H2D copy failed"; break; }
+      if (launch(c->dt[sl], c->d2[sl], c0, cnt, st, &own)) { err = g_err; break; }
+      if (hipMemcpyAsync(out + c0 * uo, c->dt[sl], cnt * uo, hipMemcpyDeviceToHost, st) != hipSuccess) { err = "D2H copy failed"; break; }
+    }
+    for (int i = 0; i < kSlots; i++) {
+      hipError_t e = hipStreamSynchronize(c->st[i]);
+      if (e != hipSuccess && err.empty()) err = std::string("kernel failed: ") + hipGetErrorString(e);
+    }
+  }
+  if (!err.empty()) return fail("device %d: %s", P->device, err.c_str());
+  return 0;
+}
+
 extern "C" int pbc_hip_host_alloc(void **out, size_t bytes) {
   if (!out) return fail("null argument");
   if (hipHostMalloc(out, bytes ? bytes : 1, hipHostMallocPortable) != hipSuccess) return fail("hipHostMalloc(%zu) failed", bytes);

@@ -358,6 +358,87 @@ __global__ void __launch_bounds__(kWide<N>, N >= 32 ? PBC_A1_WAVES : PBC_A_WAVES
   }
 }
 
+// ---- table sets (pbc_hip_pairing_pp_set_init / _apply_batch / _prod_batch; host side: pbc_hip_ppset.hip) ---------------
+// Every table of a set in ONE launch, one first argument per lane, on the lane bodies of the single-table kernels: table
+// t is tabs + t tab_words and holds the words a_pp_init_kernel / a1_pp_init_kernel write for g1[t].
+template <int N>
+__global__ void __launch_bounds__(kBlock) a_pp_set_init_kernel(uint32_t *tabs, uint32_t *flags, const uint8_t *g1, size_t m, size_t tab_words, KArgs<N> ka) {
+  size_t idx = (size_t) blockIdx.x * kBlock + threadIdx.x;
+  if (idx >= m) return;
+  flags[idx] = a_pp_init_lane<N>(tabs + idx * tab_words, g1 + idx * 2 * (size_t) fq_bytes<N>()) ? 1u : 0u;
+}
+template <int N>
+__global__ void __launch_bounds__(kBlock) a1_pp_set_init_kernel(uint32_t *tabs, uint32_t *flags, const uint8_t *g1, size_t m, size_t tab_words, KArgs<N> ka) {
+  size_t idx = (size_t) blockIdx.x * kBlock + threadIdx.x;
+  if (idx >= m) return;
+  flags[idx] = a1_pp_init_lane<N>(tabs + idx * tab_words, g1 + idx * 2 * (size_t) fq_bytes<N>()) ? 1u : 0u;
+}
+// pairing_pp_apply over the wave slots of a plan (pp_set_plan.h): every wavefront reads its slot's descriptor and runs
+// al_pp_apply_kernel's body on that slot's table, which is wave-uniform data as the single table is there.  The unit
+// range of the resident loop is 64 x slots: the two wavefronts of a workgroup may hold different tables.
+template <int N>
+__global__ void __launch_bounds__(kBlock, PBC_A_WAVES) al_pp_set_apply_kernel(uint8_t *gt, const uint32_t *__restrict__ tabs,
+                                                                               const uint32_t *__restrict__ flags, size_t tab_words,
+                                                                               const uint8_t *g2, const uint64_t *__restrict__ plan, size_t slots,
+                                                                               size_t stride, size_t tmul, unsigned *ctr, KArgs<N> ka) {
+  PBC_RESIDENT_LOOP(slots * 64, ctr) {
+    const PpSlot sl = pp_set_slot(plan, vb);
+    const size_t rec = sl.rec(stride, tmul);
+    constexpr int L = 8 * N;
+    __attribute__((aligned(16))) uint8_t out[L];
+    AL<N>::pp_apply_lane(out, tabs + sl.table * tab_words, flags[sl.table] != 0, g2 + rec * L);
+    if (sl.live()) {
+      uint4 *dst = reinterpret_cast<uint4 *>(gt + rec * L);
+      const uint4 *src = reinterpret_cast<const uint4 *>(out);
+#pragma unroll
+      for (int i = 0; i < L / 16; i++) dst[i] = src[i];
+    }
+  }
+}
+// ... and the Miller record of every term of a product over the set (AL::pp_miller_record_lane): record u m + j for
+// al_prod_finish_kernel, as al_miller_kernel leaves it
+template <int N>
+__global__ void __launch_bounds__(kBlock, PBC_A_WAVES) al_pp_set_miller_kernel(uint4 *ws, const uint32_t *__restrict__ tabs,
+                                                                                const uint32_t *__restrict__ flags, size_t tab_words,
+                                                                                const uint8_t *g2, const uint64_t *__restrict__ plan, size_t slots,
+                                                                                size_t stride, size_t tmul, unsigned *ctr, KArgs<N> ka) {
+  PBC_RESIDENT_LOOP(slots * 64, ctr) {
+    const PpSlot sl = pp_set_slot(plan, vb);
+    const size_t rec = sl.rec(stride, tmul);
+    constexpr int L = 8 * N;
+    uint4 r[AL<N>::MREC];
+    AL<N>::pp_miller_record_lane(r, tabs + sl.table * tab_words, flags[sl.table] != 0, g2 + rec * L);
+    if (sl.live()) {
+#pragma unroll
+      for (int i = 0; i < AL<N>::MREC; i++) ws[rec * AL<N>::MREC + i] = r[i];
+    }
+  }
+}
+// type a1 and the generic type a sizes: a1_pp_apply_kernel's body, slot = the wavefront's index in the launch
+template <int N>
+__global__ void __launch_bounds__(kWide<N>, N >= 32 ? PBC_A1_WAVES : PBC_A_WAVES) a1_pp_set_apply_kernel(uint8_t *gt, const uint32_t *__restrict__ tabs,
+                                                                               const uint32_t *__restrict__ flags, size_t tab_words,
+                                                                               const uint8_t *g2, const uint64_t *__restrict__ plan, size_t slots,
+                                                                               size_t stride, size_t tmul, KArgs<N> ka) {
+  const size_t slot = (size_t) blockIdx.x * (kWide<N> / 64) + (threadIdx.x >> 6);
+  if (slot >= slots) return;
+  const PpSlot sl = pp_set_slot(plan, slot);
+  const size_t rec = sl.rec(stride, tmul);
+  const int L = 2 * fq_bytes<N>();
+  __attribute__((aligned(4))) uint8_t out[8 * N];
+  __shared__ __attribute__((aligned(16))) uint32_t lds_f[kMemOperands<N> ? 72 * kWide<N> : 4];   // 33-word fields: f^2 of a step in LDS
+  a1_pp_apply_lane<N>(out, tabs + sl.table * tab_words, flags[sl.table] != 0, g2 + rec * L, kMemOperands<N> ? lds_f + threadIdx.x * 72 : nullptr);
+  if (sl.live()) {
+    if ((L & 3) == 0) {
+      uint32_t *dst = reinterpret_cast<uint32_t *>(gt + rec * L);
+      const uint32_t *src = reinterpret_cast<const uint32_t *>(out);
+      for (int i = 0; i < L / 4; i++) dst[i] = src[i];
+    } else {
+      for (int i = 0; i < L; i++) gt[rec * L + i] = out[i];
+    }
+  }
+}
+
 template <int N> __global__ void e_init_kernel(EConst *out, ERaw raw, KArgs<N> ka) {
   if (threadIdx.x || blockIdx.x) return;
   e_init_lane<N>(out, raw, c_e);
@@ -576,6 +657,48 @@ int pp_apply_launch_a(pbc_hip_pp_s *pp, void *d_gt, const void *d_g2, size_t n, 
     hipLaunchKernelGGL(a1_pp_apply_kernel<33>, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, s, (uint8_t *) d_gt, pp->tab, pp->valid,
                        (const uint8_t *) d_g2, n, kargs<33>(P));
   }
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// ---- table sets: launches (host_common.h) --------------------------------------------------------------------------
+int pp_set_init_launch_a(pbc_hip_pairing_s *P, pbc_hip_pp_set_s *set, bool a1, hipStream_t s) {
+  const dim3 grid((unsigned) ((set->m + kBlock - 1) / kBlock));
+  if (a1 && P->nlimb == 16)
+    hipLaunchKernelGGL(a1_pp_set_init_kernel<16>, grid, dim3(kBlock), 0, s, set->tabs, set->flags, (const uint8_t *) set->g1, set->m, set->tab_words, kargs<16>(P));
+  else if (a1)
+    hipLaunchKernelGGL(a1_pp_set_init_kernel<33>, grid, dim3(kBlock), 0, s, set->tabs, set->flags, (const uint8_t *) set->g1, set->m, set->tab_words, kargs<33>(P));
+  else
+    hipLaunchKernelGGL(a_pp_set_init_kernel<16>, grid, dim3(kBlock), 0, s, set->tabs, set->flags, (const uint8_t *) set->g1, set->m, set->tab_words, kargs<16>(P));
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+// every batch size on the lane kernels (the wave-per-pairing routes serve one table per launch: DESIGN.md 4.6)
+int pp_set_apply_launch_a(pbc_hip_pp_set_s *set, void *d_out, const void *d_g2, const uint64_t *d_plan, size_t slots, size_t stride, size_t tmul, hipStream_t s) {
+  pbc_hip_pairing_s *P = set->P;
+  const size_t n = slots * 64;         // (the unit range of the resident loop: PBC_RGRID)
+  if (P->type == 'a' && !P->a_generic) {
+    hipLaunchKernelGGL(al_pp_set_apply_kernel<16>, dim3(PBC_RGRID(al_pp_set_apply_kernel<16>)), dim3(kBlock), 0, s, (uint8_t *) d_out, (const uint32_t *) set->tabs,
+                       (const uint32_t *) set->flags, set->tab_words, (const uint8_t *) d_g2, d_plan, slots, stride, tmul, unit_counter(P, s), kargs<16>(P));
+  } else if (P->nlimb == 16) {
+    hipLaunchKernelGGL(a1_pp_set_apply_kernel<16>, dim3((unsigned) ((slots + 1) / 2)), dim3(kBlock), 0, s, (uint8_t *) d_out, (const uint32_t *) set->tabs,
+                       (const uint32_t *) set->flags, set->tab_words, (const uint8_t *) d_g2, d_plan, slots, stride, tmul, kargs<16>(P));
+  } else {
+    hipLaunchKernelGGL(a1_pp_set_apply_kernel<33>, dim3((unsigned) ((slots + 3) / 4)), dim3(256), 0, s, (uint8_t *) d_out, (const uint32_t *) set->tabs,
+                       (const uint32_t *) set->flags, set->tab_words, (const uint8_t *) d_g2, d_plan, slots, stride, tmul, kargs<33>(P));
+  }
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+int pp_set_records_a(pbc_hip_pp_set_s *set, void *d_gt, const void *d_g2, const uint64_t *d_plan, size_t slots, size_t nu, void *recs, hipStream_t s) {
+  pbc_hip_pairing_s *P = set->P;
+  {
+    const size_t n = slots * 64;
+    hipLaunchKernelGGL(al_pp_set_miller_kernel<16>, dim3(PBC_RGRID(al_pp_set_miller_kernel<16>)), dim3(kBlock), 0, s, (uint4 *) recs, (const uint32_t *) set->tabs,
+                       (const uint32_t *) set->flags, set->tab_words, (const uint8_t *) d_g2, d_plan, slots, set->m, (size_t) 1, unit_counter(P, s), kargs<16>(P));
+  }
+  hipLaunchKernelGGL(al_prod_finish_kernel<16>, dim3(resident_grid(P, reinterpret_cast<const void *>(&al_prod_finish_kernel<16>), nu)), dim3(kBlock), 0, s,
+                     (uint8_t *) d_gt, (const uint4 *) recs, nu, (int) set->m, unit_counter(P, s), kargs<16>(P));
   HIP_TRY(hipGetLastError());
   return 0;
 }

@@ -199,6 +199,45 @@ __global__ void __launch_bounds__(kBlock, PBC_DF_WAVES) d_pp_apply_kernel(uint8_
   }
 }
 
+// Table sets (pbc_hip_pairing_pp_set_*; host side: pbc_hip_ppset.hip): every table in one launch, one first argument per
+// lane (the lane's LDS state is sized for 128-lane workgroups); table t = tabs + t tab_words, the words d_pp_init_kernel writes
+template <int N, int DEG>
+__global__ void __launch_bounds__(kBlock) d_pp_set_init_kernel(uint32_t *tabs, uint32_t *flags, const uint8_t *g1, size_t m, size_t tab_words, KArgs<N> ka) {
+  size_t idx = (size_t) blockIdx.x * kBlock + threadIdx.x;
+  if (idx >= m) return;
+  flags[idx] = TypeMNT<N, DEG>::d_pp_init_lane(tabs + idx * tab_words, g1 + idx * 2 * (size_t) fpk<N>().fbytes) ? 1u : 0u;
+}
+// d_pp_unit on the wave slot `slot` of a plan (pp_set_plan.h, host_common.h PpSlot): the slot's table is wave-uniform
+template <int N, int DEG>
+static __device__ __forceinline__ void d_pp_set_unit(size_t slot, uint8_t *gt, const uint32_t *__restrict__ tabs, const uint32_t *__restrict__ flags, size_t tab_words,
+                                                     const uint8_t *g2, const uint64_t *__restrict__ plan, size_t stride, size_t tmul) {
+  const PpSlot sl = pp_set_slot(plan, slot);
+  const size_t rec = sl.rec(stride, tmul);
+  const int fb = (int) fpk<N>().fbytes, L2 = 2 * DEG * fb, LT = 2 * DEG * fb;
+  __attribute__((aligned(4))) uint8_t out[8 * DEG * N];
+  TypeMNT<N, DEG>::d_pp_apply_lane(out, tabs + sl.table * tab_words, flags[sl.table] != 0, g2 + rec * L2);
+  if (sl.live()) {
+    if ((LT & 3) == 0) {
+      uint32_t *dst = reinterpret_cast<uint32_t *>(gt + rec * LT);
+      const uint32_t *src = reinterpret_cast<const uint32_t *>(out);
+      for (int i = 0; i < LT / 4; i++) dst[i] = src[i];
+    } else {
+      for (int i = 0; i < LT; i++) gt[rec * LT + i] = out[i];
+    }
+  }
+}
+template <int N, int DEG>
+__global__ void __launch_bounds__(kBlock, PBC_DF_WAVES) d_pp_set_apply_kernel(uint8_t *gt, const uint32_t *__restrict__ tabs, const uint32_t *__restrict__ flags,
+                                                                              size_t tab_words, const uint8_t *g2, const uint64_t *__restrict__ plan, size_t slots,
+                                                                              size_t stride, size_t tmul, unsigned *ctr, KArgs<N> ka) {
+  if constexpr (kDResident<N, DEG>) {
+    PBC_RESIDENT_LOOP(slots * 64, ctr) d_pp_set_unit<N, DEG>(vb, gt, tabs, flags, tab_words, g2, plan, stride, tmul);
+  } else {
+    const size_t slot = (size_t) blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+    if (slot < slots) d_pp_set_unit<N, DEG>(slot, gt, tabs, flags, tab_words, g2, plan, stride, tmul);
+  }
+}
+
 template <int N, int DEG> __global__ void d_init_stage1(DConst *out, DRaw raw, KArgs<N> ka) {
   if (threadIdx.x || blockIdx.x) return;
   TypeMNT<N, DEG>::init_stage1(out, raw, c_d);
@@ -309,6 +348,23 @@ int pp_apply_launch_d(pbc_hip_pp_s *pp, void *d_gt, const void *d_g2, size_t n, 
   }
   PBC_DISPATCH_D(P, hipLaunchKernelGGL((d_pp_apply_kernel<N, DEG>), dim3(kDResident<N, DEG> ? PBC_RGRID(d_pp_apply_kernel<N, DEG>) : grid), dim3(kBlock), 0, s, (uint8_t *) d_gt,
                                            pp->tab, pp->valid, (const uint8_t *) d_g2, n, kDResident<N, DEG> ? unit_counter(P, s) : nullptr, kargs<N>(P)));
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+int pp_set_init_launch_d(pbc_hip_pairing_s *P, pbc_hip_pp_set_s *set, hipStream_t s) {
+  PBC_DISPATCH_D(P, hipLaunchKernelGGL((d_pp_set_init_kernel<N, DEG>), dim3((unsigned) ((set->m + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, set->tabs, set->flags,
+                                       (const uint8_t *) set->g1, set->m, set->tab_words, kargs<N>(P)));
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+// every batch size on the lane kernel (the wave kernels serve one table per launch: DESIGN.md 4.6)
+int pp_set_apply_launch_d(pbc_hip_pp_set_s *set, void *d_out, const void *d_g2, const uint64_t *d_plan, size_t slots, size_t stride, size_t tmul, hipStream_t s) {
+  pbc_hip_pairing_s *P = set->P;
+  const size_t n = slots * 64;         // (the unit range of the resident loop: PBC_RGRID)
+  PBC_DISPATCH_D(P, hipLaunchKernelGGL((d_pp_set_apply_kernel<N, DEG>), dim3(kDResident<N, DEG> ? PBC_RGRID(d_pp_set_apply_kernel<N, DEG>) : (unsigned) ((slots + 1) / 2)),
+                                       dim3(kBlock), 0, s, (uint8_t *) d_out, (const uint32_t *) set->tabs, (const uint32_t *) set->flags, set->tab_words,
+                                       (const uint8_t *) d_g2, d_plan, slots, stride, tmul, kDResident<N, DEG> ? unit_counter(P, s) : nullptr, kargs<N>(P)));
   HIP_TRY(hipGetLastError());
   return 0;
 }

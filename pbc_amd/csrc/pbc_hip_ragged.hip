@@ -63,6 +63,26 @@ __global__ void __launch_bounds__(kBlock, 2) ragged_gt_finish_kernel(uint8_t *gt
     }                                                                                                                         \
   } while (0)
 
+// The folds and the finish of the GT route on records and flag bytes that are in place (host_common.h; also the tail of
+// a product over a table set, pbc_hip_ppset.hip): one fold kernel per level, the records ping-pong between the two areas
+int ragged_gt_reduce(pbc_hip_pairing_s *P, void *d_gt, void *cur_, void *fcur_, void *nxt_, void *fnxt_, const uint64_t *const *d_plan,
+                     const size_t *sizes, int nl, size_t n, unsigned F, hipStream_t s) {
+  uint8_t *cur = (uint8_t *) cur_, *nxt = (uint8_t *) nxt_, *fcur = (uint8_t *) fcur_, *fnxt = (uint8_t *) fnxt_;
+  for (int l = 0; l + 1 < nl; l++) {
+    const size_t nout = sizes[(size_t) l + 1];
+    const unsigned grid = (unsigned) ((nout + kBlock - 1) / kBlock);
+    PBC_RAGGED_DISPATCH(P, hipLaunchKernelGGL(ragged_gt_fold_kernel<G>, dim3(grid), dim3(kBlock), 0, s, nxt, fnxt, (const uint8_t *) cur, (const uint8_t *) fcur,
+                                              d_plan[(size_t) l], d_plan[(size_t) l + 1], n, nout, F, kargs<G::NW>(P)));
+    std::swap(cur, nxt);
+    std::swap(fcur, fnxt);
+  }
+  const unsigned grid = (unsigned) ((n + kBlock - 1) / kBlock);
+  PBC_RAGGED_DISPATCH(P, hipLaunchKernelGGL(ragged_gt_finish_kernel<G>, dim3(grid), dim3(kBlock), 0, s, (uint8_t *) d_gt, (const uint8_t *) cur, (const uint8_t *) fcur,
+                                            d_plan[(size_t) nl - 1], n, kargs<G::NW>(P)));
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
 static size_t ws_round(size_t b) { return (b + 255) & ~(size_t) 255; }
 static bool record_route(const pbc_hip_pairing_s *P) { return P->type == 'a' && !P->a_generic; }
 
@@ -111,19 +131,7 @@ static int ragged_group(pbc_hip_pairing_s *P, uint8_t *d_gt, const uint8_t *d_g1
     const unsigned grid = (unsigned) ((T + kBlock - 1) / kBlock);
     PBC_RAGGED_DISPATCH(P, hipLaunchKernelGGL((ragged_flag_kernel<F1, F2>), dim3(grid), dim3(kBlock), 0, s, fcur, d_g1, d_g2, T, kargs<F1::NW>(P)));
   }
-  for (int l = 0; l + 1 < nl; l++) {
-    const size_t nout = sizes[(size_t) l + 1];
-    const unsigned grid = (unsigned) ((nout + kBlock - 1) / kBlock);
-    PBC_RAGGED_DISPATCH(P, hipLaunchKernelGGL(ragged_gt_fold_kernel<G>, dim3(grid), dim3(kBlock), 0, s, nxt, fnxt, (const uint8_t *) cur, (const uint8_t *) fcur,
-                                              d_plan[(size_t) l], d_plan[(size_t) l + 1], n, nout, F, kargs<G::NW>(P)));
-    std::swap(cur, nxt);
-    std::swap(fcur, fnxt);
-  }
-  const unsigned grid = (unsigned) ((n + kBlock - 1) / kBlock);
-  PBC_RAGGED_DISPATCH(P, hipLaunchKernelGGL(ragged_gt_finish_kernel<G>, dim3(grid), dim3(kBlock), 0, s, d_gt, (const uint8_t *) cur, (const uint8_t *) fcur,
-                                            d_plan[(size_t) nl - 1], n, kargs<G::NW>(P)));
-  HIP_TRY(hipGetLastError());
-  return 0;
+  return ragged_gt_reduce(P, d_gt, cur, fcur, nxt, fnxt, d_plan.data(), sizes.data(), nl, n, F, s);
 }
 // a call whose terms exceed kRaggedMaxTerms: launch groups that end at product boundaries, one after the other on s
 int ragged_launch(pbc_hip_pairing_s *P, void *d_gt, const void *d_g1, const void *d_g2, const uint64_t *offsets, size_t n,
