@@ -44,6 +44,8 @@
  *     Miller loop runs through V = O or V = +-P, where the reference divides by zero.  element_mul_zn is exact
  *     for them.
  *   - Coordinates >= q are reduced mod q on load, as fp_from_bytes does (montfp.c:498-517).
+ * Which of these classes a record belongs to -- off the curve, O, inside or outside the subgroup [r] P = O; for GT: zero,
+ * 1, x^r = 1 or not -- is what pbc_hip_element_membership_batch reports, one byte per record, without changing it.
  */
 #ifndef PBC_HIP_H
 #define PBC_HIP_H
@@ -395,6 +397,37 @@ int pbc_hip_is_almost_coddh_batch(pbc_hip_pairing_t *p, uint8_t *res, const uint
                                   const uint8_t *c, const uint8_t *d, size_t n, int mode);
 int pbc_hip_is_almost_coddh_batch_dev(pbc_hip_pairing_t *p, void *d_res, const void *d_a, const void *d_b,
                                       const void *d_c, const void *d_d, size_t n, int mode, void *stream);
+
+/* Membership verdicts for records of G1, G2 (group 1, 2) and GT (group 3, as in pbc_hip_element_pp_init), classified on the
+ * device.  curve_from_bytes (ecc/curve.c:609-623) checks the curve equation only (curve_is_valid_point, ecc/curve.c:57-77)
+ * and turns off-curve bytes into O silently; element_from_bytes_compressed / _x_only rebuild a point of the WHOLE curve from
+ * any x; G2 of types d, f, g is the whole twist; a GT record is whatever field element its bytes spell.  A PBC program
+ * that wants to know multiplies by the group order -- element_mul_mpz(t, P, pairing->r) and element_is0(t), on GT
+ * element_pow_mpz(t, x, pairing->r) and element_is1(t) (pairing->r: include/pbc_pairing.h; type a1: the composite n) --
+ * and this call is that idiom over a batch.  in: n records in the wire format of the other entry points, read as they
+ * read them (coordinates reduced mod q on load; a point whose reduced coordinates are all zero is O -- on types a / a1
+ * that includes the 2-torsion point (0, 0), "Zero-filled records" above; the curve test is curve_is_valid_point on E for
+ * G1 and on the twist for G2 of types d, f, g).  res: n bytes, each exactly one of the four values below; nothing else is
+ * written, the records are not changed.
+ * INSIDE says exactly "[r] P = O" (GT: x^r = 1).  It does NOT say "P is a multiple of the generator": on type e (k = 1:
+ * E(F_q)[r] has r^2 points) and wherever the r-torsion of the curve or twist is larger than one cyclic group, every point
+ * of that torsion is INSIDE.
+ * The point kernels run a Jacobian ladder over r's signed digits (already in every family's constant block) up to
+ * [r - 1] P and compare that with -P projectively: no table, no inversion; a lane whose ladder meets an exceptional step
+ * (points of small or crafted order) is decided by a second pass over the complete group law, as in
+ * pbc_hip_element_mul_zn_batch ("hip_group_slow 1" in the parameter text sends every lane there).  GT: x^r with r taken
+ * from the same constants; the 512-bit type a field uses the Lucas ladder for elements of norm 1 and the generic power for
+ * the others.
+ * group outside 1..3 and null pointers with n > 0 are errors; n == 0 succeeds and touches nothing.
+ * Host-buffer form: range split over the device set and staged, as pbc_hip_element_mul_zn_batch.  _dev form:
+ * device-resident buffers, enqueued on `stream`, asynchronous; it takes the (device, stream) workspace and its issue lock
+ * like the other group operations. */
+#define PBC_HIP_MEMBER_INVALID   0  /* G1/G2: not on the curve.   GT: the zero element            */
+#define PBC_HIP_MEMBER_OUTSIDE   1  /* on the curve / a unit, but [r]P != O  /  x^r != 1          */
+#define PBC_HIP_MEMBER_INSIDE    2  /* [r]P == O, P != O          /  x^r == 1, x != 1             */
+#define PBC_HIP_MEMBER_IDENTITY  3  /* the identity: O / 1                                         */
+int pbc_hip_element_membership_batch(pbc_hip_pairing_t *p, int group, uint8_t *res, const uint8_t *in, size_t n);
+int pbc_hip_element_membership_batch_dev(pbc_hip_pairing_t *p, int group, void *d_res, const void *d_in, size_t n, void *stream);
 
 /* Fixed-base powers: replace element_pp_init / element_pp_pow_zn / element_pp_clear (include/pbc_field.h:591-625 ->
  * element_build_base_table / element_pow_base_table, arith/field.c:243-323: a table of in^(w 2^(5 i)), a power = a product

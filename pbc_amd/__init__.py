@@ -148,6 +148,8 @@ def lib():
         L.pbc_hip_diag_pp_set_plan.argtypes = [vp, vp, sz, vp, sz]
         L.pbc_hip_pairing_pp_set_prod_batch.argtypes = [vp, vp, vp, sz]
         L.pbc_hip_pairing_pp_set_prod_batch_dev.argtypes = [vp, vp, vp, sz, vp]
+        L.pbc_hip_element_membership_batch.argtypes = [vp, ci, vp, vp, sz]
+        L.pbc_hip_element_membership_batch_dev.argtypes = [vp, ci, vp, vp, sz, vp]
         _lib = L
     return _lib
 
@@ -186,6 +188,7 @@ EXPORTS = (
     "pbc_hip_pairing_pp_set_init", "pbc_hip_pairing_pp_set_init_dev", "pbc_hip_pairing_pp_set_clear", "pbc_hip_pairing_pp_set_count",
     "pbc_hip_pairing_pp_set_apply_batch", "pbc_hip_pairing_pp_set_apply_batch_dev", "pbc_hip_diag_pp_set_plan",
     "pbc_hip_pairing_pp_set_prod_batch", "pbc_hip_pairing_pp_set_prod_batch_dev",
+    "pbc_hip_element_membership_batch", "pbc_hip_element_membership_batch_dev",
 )
 
 
@@ -201,6 +204,7 @@ def param_text(name):
 
 
 CODDH_ALMOST, CODDH_EXACT = 0, 1     # PBC_HIP_CODDH_* (include/pbc_hip.h)
+MEMBER_INVALID, MEMBER_OUTSIDE, MEMBER_INSIDE, MEMBER_IDENTITY = 0, 1, 2, 3     # PBC_HIP_MEMBER_* (include/pbc_hip.h)
 ZR_OPS = {"mul": 0, "add": 1, "sub": 2, "invert": 3, "neg": 4, "halve": 5, "double": 6, "div": 7}   # pbc_hip_zr_op_batch
 
 
@@ -402,6 +406,27 @@ class Pairing:
         mode = CODDH_EXACT if exact else CODDH_ALMOST
         if lib().pbc_hip_is_almost_coddh_batch_dev(self._h, d_res, d_a, d_b, d_c, d_d, n, mode, stream):
             raise PbcHipError("is_almost_coddh_dev: " + _err())
+
+    # ---- verdicts: membership of G1 / G2 / GT records (include/pbc_hip.h) -------------------------
+    def element_membership(self, group, recs):
+        """res[i] = MEMBER_INVALID (off the curve; GT: zero), MEMBER_OUTSIDE ([r] P != O; x^r != 1), MEMBER_INSIDE or
+        MEMBER_IDENTITY for records of G1 / G2 / GT (group 1 / 2 / 3).  Returns an np.uint8 array of shape (n,)."""
+        import numpy as np
+        if group not in (1, 2, 3):
+            raise PbcHipError("element_membership: group must be 1, 2 or 3 (GT)")
+        recs = np.ascontiguousarray(recs, dtype=np.uint8)
+        lrec = self._group_len(group)
+        n = recs.size // lrec
+        if recs.size != n * lrec:
+            raise ValueError("records must be n records of the group's length")
+        res = np.empty(n, np.uint8)
+        if lib().pbc_hip_element_membership_batch(self._h, group, _np_ptr(res), _np_ptr(recs), n):
+            raise PbcHipError("element_membership: " + _err())
+        return res
+
+    def element_membership_dev(self, group, d_res, d_in, n, stream=0):
+        if lib().pbc_hip_element_membership_batch_dev(self._h, group, d_res, d_in, n, stream):
+            raise PbcHipError("element_membership_dev: " + _err())
 
     # ---- text formats (host side; include/pbc_hip.h) ------------------------------------------
     def _group_len(self, group):

@@ -339,9 +339,12 @@ static int init_type_a(pbc_hip_pairing_s *P, const char *txt, size_t len) {
     P->nlimb = q.bits() <= 512 ? 16 : 33;
     P->a_generic = true;
     if (P->nlimb == 16) ag_aux_build<16>(P, q, txt, len); else ag_aux_build<33>(P, q, txt, len);
-    P->a.rbits = pbc_host::naf_of_half(r, P->a.r, P->a.rm, 34);      // signed digits: three for a Solinas r
-    if (!P->a.rbits) return fail("type a: r too wide for the Miller loop digits");
   }
+  // signed digits of r: three for a Solinas r.  The Miller loops of the generic type a kernels read them (a_generic; the
+  // fast path has its Solinas loop and reads none of r / rm / rbits), and so do the membership ladders on every path
+  // (group_member.cuh)
+  P->a.rbits = pbc_host::naf_of_half(r, P->a.r, P->a.rm, 34);
+  if (!P->a.rbits) return fail("type a: r too wide for the Miller loop digits");
   // work model: SURVEY.md 8d instrumented the reference on a.param (exp2 = 159, 353-bit h): 3675 F_q
   // products in a_pairing_proj's Miller loop + 717 in a_tateexp; a_pairings_affine (a_param.c:1283-1383)
   // 41377 for k = 16 (linear model 2543 k + 689); a_pairing_pp_apply 1838.
