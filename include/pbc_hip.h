@@ -429,6 +429,47 @@ int pbc_hip_is_almost_coddh_batch_dev(pbc_hip_pairing_t *p, void *d_res, const v
 int pbc_hip_element_membership_batch(pbc_hip_pairing_t *p, int group, uint8_t *res, const uint8_t *in, size_t n);
 int pbc_hip_element_membership_batch_dev(pbc_hip_pairing_t *p, int group, void *d_res, const void *d_in, size_t n, void *stream);
 
+/* One integer of any length for a whole batch: element_mul_mpz / element_pow_mpz (include/pbc_field.h:292, :365; on a
+ * curve group curve.c:713 f->mul_mpz = element_pow_mpz, on GT ecc/pairing.c:215,266,274 -- one routine, so one entry point).
+ * group 1, 2: out[i] = [k] in[i]; group 3: out[i] = in[i]^k.  The calls above take one Z_r record PER UNIT; this one takes
+ * ONE k for all n units -- signing with one secret key, blinding a batch with one factor, one public exponent -- and a k
+ * of any length: clearing a cofactor, multiplying by the curve order #E, projecting into a subgroup of a composite-order
+ * curve are integers above r that no Z_r record holds.
+ * k: a NON-NEGATIVE integer as a big-endian magnitude of klen bytes, 0 <= klen <= PBC_HIP_MPZ_MAX_BYTES; leading zero bytes
+ * are allowed; klen == 0 or zero bytes only: k = 0; k may be NULL only when klen == 0.  k is HOST memory in both forms
+ * and is read before the call returns (the rule of the ragged products' offsets).  Negative integers are not part of
+ * the contract: the reference walks mpz_tstbit of the two's complement (arith/field.c:113-126), its result for them is
+ * not defined, and there is no way to pass a sign here.
+ * Points: records are read as pbc_hip_element_mul_zn_batch reads them (coordinates reduced mod q, an off-curve record is
+ * O, the all-zero record is O); ANY point of the curve is accepted -- the whole of E(F_q), the whole twist for G2 of types
+ * d, f, g -- and k is NOT reduced mod r: it is taken as the integer stands.  The result is affine, O is zero bytes.  Whenever
+ * k fits a Z_r record the bytes are those of pbc_hip_element_mul_zn_batch with k replicated n times.
+ * GT: every element of the field is accepted, no subgroup is assumed: x^0 = 1, 0^0 = 1 (arith/field.c:117), 0^k = 0 for
+ * k > 0.
+ * The host recodes k ONCE into signed digits (points: non-adjacent form, plain or of width 4; GT: the bits) and every lane walks the same
+ * string, so the kernels branch on a wave-uniform digit: one doubling per digit, one addition only where the shared
+ * digit is non-zero.  A lane whose ladder meets an exceptional step or ends in O is redone by a second pass over the same
+ * digits on the complete group law, as in pbc_hip_element_mul_zn_batch ("hip_group_slow 1" sends every lane there); the
+ * 512-bit type a field powers GT elements of norm 1 with the Lucas ladder behind a per-lane test of the norm, and type f
+ * on the five-word field hands a dense k that fits a Z_r record to the cyclotomic lane of pbc_hip_element_pow_zn_GT_batch
+ * behind its per-lane membership test; every other element takes the generic power.
+ * out == in (exactly) is allowed; n == 0 returns 0 and touches nothing.  Errors (non-zero, pbc_hip_last_error) are found
+ * before a device is looked for: null arguments, group outside 1..3, klen > PBC_HIP_MPZ_MAX_BYTES.
+ * Host-buffer form: range split over the device set and staged, as pbc_hip_element_mul_zn_batch.  _dev form:
+ * device-resident records, enqueued on `stream`, asynchronous; the digits reach the device by a stream-ordered copy, so
+ * calls with different k enqueued back to back on one stream each see their own.
+ * pbc_hip_diag_mpz_digits (pure host, for the tests): the digit string of k for width w -- w = 1 the bits, w >= 2 the
+ * width-w non-adjacent form (digits zero or odd, |d| < 2^(w-1), at most 8 klen + 1 of them), w = 0 the string a call on
+ * points runs on (w = 2, or w = 4 with a per-lane table of P, 3P, 5P, 7P where that saves more additions than the table
+ * costs) -- digit i (weight 2^i) at out[i], the first `cap` of them; returns their number (0 for k = 0 and for
+ * arguments outside the contract). */
+#define PBC_HIP_MPZ_MAX_BYTES 512
+int pbc_hip_element_mul_mpz_batch(pbc_hip_pairing_t *p, int group, uint8_t *out, const uint8_t *in,
+                                  const uint8_t *k, size_t klen, size_t n);
+int pbc_hip_element_mul_mpz_batch_dev(pbc_hip_pairing_t *p, int group, void *d_out, const void *d_in,
+                                      const uint8_t *k /* HOST memory */, size_t klen, size_t n, void *stream);
+size_t pbc_hip_diag_mpz_digits(const uint8_t *k, size_t klen, int w, int8_t *out, size_t cap);
+
 /* Fixed-base powers: replace element_pp_init / element_pp_pow_zn / element_pp_clear (include/pbc_field.h:591-625 ->
  * element_build_base_table / element_pow_base_table, arith/field.c:243-323: a table of in^(w 2^(5 i)), a power = a product
  * of table entries) for a base in G1, G2 (group 1, 2) or GT (group 3) -- the BLS shape: one generator, many secret keys or

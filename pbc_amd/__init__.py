@@ -150,6 +150,10 @@ def lib():
         L.pbc_hip_pairing_pp_set_prod_batch_dev.argtypes = [vp, vp, vp, sz, vp]
         L.pbc_hip_element_membership_batch.argtypes = [vp, ci, vp, vp, sz]
         L.pbc_hip_element_membership_batch_dev.argtypes = [vp, ci, vp, vp, sz, vp]
+        L.pbc_hip_element_mul_mpz_batch.argtypes = [vp, ci, vp, vp, vp, sz, sz]
+        L.pbc_hip_element_mul_mpz_batch_dev.argtypes = [vp, ci, vp, vp, vp, sz, sz, vp]
+        L.pbc_hip_diag_mpz_digits.restype = sz
+        L.pbc_hip_diag_mpz_digits.argtypes = [vp, sz, ci, vp, sz]
         _lib = L
     return _lib
 
@@ -189,6 +193,7 @@ EXPORTS = (
     "pbc_hip_pairing_pp_set_apply_batch", "pbc_hip_pairing_pp_set_apply_batch_dev", "pbc_hip_diag_pp_set_plan",
     "pbc_hip_pairing_pp_set_prod_batch", "pbc_hip_pairing_pp_set_prod_batch_dev",
     "pbc_hip_element_membership_batch", "pbc_hip_element_membership_batch_dev",
+    "pbc_hip_element_mul_mpz_batch", "pbc_hip_element_mul_mpz_batch_dev", "pbc_hip_diag_mpz_digits",
 )
 
 
@@ -204,6 +209,7 @@ def param_text(name):
 
 
 CODDH_ALMOST, CODDH_EXACT = 0, 1     # PBC_HIP_CODDH_* (include/pbc_hip.h)
+MPZ_MAX_BYTES = 512                                                             # PBC_HIP_MPZ_MAX_BYTES (include/pbc_hip.h)
 MEMBER_INVALID, MEMBER_OUTSIDE, MEMBER_INSIDE, MEMBER_IDENTITY = 0, 1, 2, 3     # PBC_HIP_MEMBER_* (include/pbc_hip.h)
 ZR_OPS = {"mul": 0, "add": 1, "sub": 2, "invert": 3, "neg": 4, "halve": 5, "double": 6, "div": 7}   # pbc_hip_zr_op_batch
 
@@ -427,6 +433,48 @@ class Pairing:
     def element_membership_dev(self, group, d_res, d_in, n, stream=0):
         if lib().pbc_hip_element_membership_batch_dev(self._h, group, d_res, d_in, n, stream):
             raise PbcHipError("element_membership_dev: " + _err())
+
+    # ---- one integer of any length for the whole batch (include/pbc_hip.h) -------------------------
+    @staticmethod
+    def _mpz_bytes(k):
+        """a Python int -> the big-endian magnitude the C-ABI takes (k = 0: no bytes)"""
+        k = int(k)
+        if k < 0:
+            raise ValueError("element_mul_mpz: k must be non-negative")
+        return k.to_bytes((k.bit_length() + 7) // 8, "big")
+
+    def element_mul_mpz(self, group, recs, k):
+        """out[i] = [k] recs[i] on G1 / G2 (group 1 / 2), recs[i]^k on GT (group 3) for ONE non-negative Python int k of
+        up to MPZ_MAX_BYTES bytes, taken as it stands (not reduced mod r); any point of the curve, any field element."""
+        import numpy as np
+        kb = self._mpz_bytes(k)
+        if group not in (1, 2, 3):
+            raise PbcHipError("element_mul_mpz: group must be 1, 2 or 3 (GT)")
+        recs = np.ascontiguousarray(recs, dtype=np.uint8)
+        lrec = self._group_len(group)
+        n = recs.size // lrec
+        if recs.size != n * lrec:
+            raise ValueError("element_mul_mpz: %d bytes are no whole number of %d-byte records" % (recs.size, lrec))
+        out = np.empty((n, lrec), np.uint8)
+        if lib().pbc_hip_element_mul_mpz_batch(self._h, group, _np_ptr(out), _np_ptr(recs), kb, len(kb), n):
+            raise PbcHipError("element_mul_mpz: " + _err())
+        return out
+
+    def element_mul_mpz_dev(self, group, d_out, d_in, k, n, stream=0):
+        kb = self._mpz_bytes(k)
+        if lib().pbc_hip_element_mul_mpz_batch_dev(self._h, group, d_out, d_in, kb, len(kb), n, stream):
+            raise PbcHipError("element_mul_mpz_dev: " + _err())
+
+    @staticmethod
+    def mpz_digits(k, w):
+        """the digit string the kernels walk for k (pbc_hip_diag_mpz_digits): w = 1 the bits (GT), w >= 2 the width-w
+        non-adjacent form, w = 0 the library's own choice for a call on points (w = 2 or 4, by k); digit i has weight 2^i.
+        Returns an np.int8 array."""
+        import numpy as np
+        kb = Pairing._mpz_bytes(k)
+        out = np.zeros(8 * len(kb) + 1, np.int8)
+        n = lib().pbc_hip_diag_mpz_digits(kb, len(kb), w, _np_ptr(out), out.size)
+        return out[:n].copy()
 
     # ---- text formats (host side; include/pbc_hip.h) ------------------------------------------
     def _group_len(self, group):
