@@ -500,7 +500,7 @@ int pbc_hip_finalpow_batch(pbc_hip_pairing_t *p, uint8_t *out, const uint8_t *in
  * curve.c:603-609).  The change of Montgomery radix is one F_q product per coordinate on the device; everything else
  * (off-curve inputs -> O, identity outputs, products) is the wire-format path.  Replaces, for the batch calls of
  * integration/pbc_hip_glue.c, fp_to_bytes / fp_from_bytes on every coordinate. */
-/* Diagnostic (tests): a schedule the wavefront kernels of type d interpret for this object (csrc/dw_sched.h: which level of
+/* Diagnostic (tests): a schedule the wavefront kernels of type d interpret for this object (csrc/dw_sched.h, entry format in csrc/wave_sched.h: which level of
  * which program runs when, flattened by the host from the signed digits of r and the bits of Phi_6(q) / r -- the walk of
  * cc_miller_no_denom_affine, ecc/d_param.c:321-422, and lucas_even, :462-482).  which = 0: element_pairing; 1: the Miller
  * value of one term of element_prod_pairing; 2: the product with a term's value + the final exponentiation; 3:

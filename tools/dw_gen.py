@@ -519,7 +519,7 @@ class Model:
                     writes.append((n.slot, acc % self.q))
         names_written = [w[0] for w in writes]
         assert len(set(names_written)) == len(names_written), names_written
-        # an eight-term level deals FOUR lanes to a sum (pairing_dw.cuh exec_split8): sixteen sums in all, both tracks together
+        # an eight-term level deals FOUR lanes to a sum (wave_vm.cuh exec_split8): sixteen sums in all, both tracks together
         if any(len(n.terms) > 4 for tr in tracks for p, lev in tr for n in p.levels[lev]):
             assert sum(len(p.levels[lev]) for tr in tracks for p, lev in tr) <= 16, [(p.name, lev) for tr in tracks for p, lev in tr]
         for s, v in writes:
@@ -746,7 +746,7 @@ OPS = {"level": 0, "bzero": 1, "inv": 2, "end": 3, "loadline": 4}
 
 
 def pack_entry(progs_index, a, b, op=0, load=None):
-    """the 64-bit schedule entry of dw_sched.h: row a | lanes a | row b | lanes b | terms | op | table line | line flag"""
+    """the 64-bit schedule entry of wave_sched.h: row a | lanes a | row b | lanes b | terms | op | table line | line flag"""
     ra, la, ta = progs_index[a] if a else (0, 0, 0)
     rb, lb, tb = progs_index[b] if b else (0, 0, 0)
     e = ra | la << 12 | rb << 17 | lb << 29 | max(ta if la else 0, tb if lb else 0) << 34 | op << 38
@@ -852,8 +852,9 @@ def emit(progs):
     """rows of five dwords per sum: out | x0..x7 | y0..y7 as bytes (unused terms: the ZERO slot); a level = (first row, T, lanes)"""
     out = ["// dw_tables.h -- GENERATED by tools/dw_gen.py (do not edit): the level programs of the wave-per-pairing type d kernel",
            "// (pairing_dw.cuh).  One ROW of five dwords per sum: the slot it writes, eight x operands, eight y operands, one byte each",
-           "// (terms a sum does not have name the ZERO slot); a LEVEL is (first row, terms per sum, working lanes).",
-           "#pragma once", "#include <stdint.h>", "namespace pbc { namespace dw {",
+           "// (terms a sum does not have name the ZERO slot); a LEVEL is (first row, terms per sum, working lanes).  The machine:",
+           "// wave_vm.cuh; the schedule entry, its ops and LevelRef: wave_sched.h.",
+           "#pragma once", "#include \"wave_sched.h\"", "namespace pbc { namespace dw {",
            "constexpr int kSlots = %d;" % len(SLOTS.order)]
     keep = lambda n: "." not in n or n.split(".")[0] in ("f", "L0", "L1", "V0", "V1")
     out.append("enum Slot : int { " + ", ".join("S_%s = %d" % (n.replace(".", "_"), i) for i, n in enumerate(SLOTS.order) if keep(n)) + " };")
@@ -868,11 +869,9 @@ def emit(progs):
                 b = [o] + xs + [z] * (8 - len(xs)) + ys + [z] * (8 - len(ys)) + [0, 0, 0]
                 rows.append([b[4 * i] | b[4 * i + 1] << 8 | b[4 * i + 2] << 16 | b[4 * i + 3] << 24 for i in range(5)])
         out.append("constexpr int P_%s = %d, N_%s = %d;" % (name, first, name, len(tab)))
-    out.append("enum { OP_LEVEL = 0, OP_BZERO = 1, OP_INV = 2, OP_END = 3, OP_LOADLINE = 4 };      // schedule entries (dw_sched.h)")
-    out.append("struct LevelRef { uint16_t row; uint8_t T, lanes; };")
     out.append("constexpr int kLevels = %d, kRows = %d;" % (len(index), len(rows)))
     out.append("// (the level table is read by the HOST: it flattens a pairing into a schedule of packed entries, dw_sched.h)")
-    out.append("static const LevelRef h_level[kLevels] = {" + ", ".join("{%d, %d, %d}" % x for x in index) + "};")
+    out.append("static const wave::LevelRef h_level[kLevels] = {" + ", ".join("{%d, %d, %d}" % x for x in index) + "};")
     out.append("__device__ const uint32_t g_rows[kRows * 5] = {" + ",".join("0x%xu" % w for r in rows for w in r) + "};")
     out.append("} }  // namespace pbc::dw")
     return "\n".join(out) + "\n"

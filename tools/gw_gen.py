@@ -640,18 +640,15 @@ def emit(progs):
     rows, index, pidx = tables(progs)
     keep = lambda n: not (n.split(".")[0] in ("ft", "pt") and ".t" in n)
     out = ["// gw_tables.h -- GENERATED by tools/gw_gen.py (do not edit): the level programs of the wave-per-pairing type g kernel",
-           "// (pairing_gw.cuh) for the machine of pairing_dw.cuh.  One ROW of five dwords per sum: the slot it writes, eight x operands, eight",
+           "// (pairing_gw.cuh) for the machine of wave_vm.cuh.  One ROW of five dwords per sum: the slot it writes, eight x operands, eight",
            "// y operands, one byte each (terms a sum does not have name the ZERO slot); a LEVEL is (first row, terms per sum, working lanes);",
            "// a PROGRAM is a run of levels, found by name by the host (gw_sched.h).",
-           "#pragma once", "#include <stdint.h>", "namespace pbc { namespace gw {",
+           "#pragma once", "#include \"wave_sched.h\"", "namespace pbc { namespace gw {",
            "constexpr int kSlots = %d;" % len(SLOTS.order)]
     out.append("enum Slot : int { " + ", ".join("S_%s = %d" % (n.replace(".", "_"), i) for i, n in enumerate(SLOTS.order) if keep(n)) + " };")
-    out.append("enum { OP_LEVEL = 0, OP_BZERO = 1, OP_INV = 2, OP_END = 3, OP_LOADLINE = 4, OP_MARK = 5 };      // schedule entries (gw_sched.h; dw_tables.h's values)")
-    out.append("struct LevelRef { uint16_t row; uint8_t T, lanes; };")
-    out.append("struct ProgRef { const char *name; uint16_t first, count; };")
     out.append("constexpr int kProgs = %d, kLevels = %d, kRows = %d;" % (len(pidx), len(index), len(rows)))
-    out.append("static const ProgRef h_prog[kProgs] = {" + ", ".join('{"%s", %d, %d}' % x for x in pidx) + "};")
-    out.append("static const LevelRef h_level[kLevels] = {" + ", ".join("{%d, %d, %d}" % x for x in index) + "};")
+    out.append("static const wave::ProgRef h_prog[kProgs] = {" + ", ".join('{"%s", %d, %d}' % x for x in pidx) + "};")
+    out.append("static const wave::LevelRef h_level[kLevels] = {" + ", ".join("{%d, %d, %d}" % x for x in index) + "};")
     out.append("__device__ const uint32_t g_rows[kRows * 5] = {" + ",".join("0x%xu" % w for r in rows for w in r) + "};")
     out.append("} }  // namespace pbc::gw")
     return "\n".join(out) + "\n"
