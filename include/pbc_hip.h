@@ -484,6 +484,50 @@ int pbc_hip_element_pp_init(pbc_hip_element_pp_t **pp, pbc_hip_pairing_t *p, int
 void pbc_hip_element_pp_clear(pbc_hip_element_pp_t *pp);
 int pbc_hip_element_pp_pow_zn_batch(pbc_hip_element_pp_t *pp, uint8_t *out, const uint8_t *zr, size_t n);
 int pbc_hip_element_pp_pow_zn_batch_dev(pbc_hip_element_pp_t *pp, void *d_out, const void *d_zr, size_t n, void *stream);
+/* Sets of fixed-base tables: m bases of one group in ONE object -- element_pp_init / element_pp_pow_zn
+ * (include/pbc_field.h:591-625 -> element_build_base_table / element_pow_base_table, arith/field.c:243-323) once per base,
+ * and element_mul on the results (include/pbc_field.h:280).  The shape of BBS+ / Pointcheval-Sanders signatures
+ * (h_0 + sum [m_j] h_j), Waters' hash, Pedersen and vector commitments, KZG commitments to a fixed SRS and ABE encryption
+ * over fixed public parameters: SEVERAL fixed generators, many scalar vectors.  The group-side twin of
+ * pbc_hip_pairing_pp_set_* above.
+ *   `group` is 1, 2 (the twists of types d, f, g included) or 3 (GT); every family works, nothing is refused by type.
+ *   Table t holds exactly the words pbc_hip_element_pp_init derives from bases[t]: length_in_bytes_Zr rows of 255 affine
+ *   entries [w 2^(8 row)] B_t in Montgomery words (GT: 256 entries B_t^(w 2^(8 row)), w = 0 the identity).  All tables sit in
+ *   ONE device allocation, together with a copy of the m base records and one "complete only" flag per table, set for a
+ *   base of small order (some entry is O) or off the curve (which reads as O).  ONE launch builds all m tables, one entry
+ *   per lane.  About 0.65 MB per base on a.param, 8-9 MB per base on a1.param.  The set lives on the device the pairing
+ *   object was created on; a device set on the object is not used.  _init_dev takes device records and is asynchronous
+ *   on `stream`; the flags the host needs are read back before the first call that uses them (that call waits for the
+ *   table kernel), not in _init_dev.
+ *   pow_zn: out[u] = [zr[u]] B_t (GT: B_t^zr[u]) for offsets[t] <= u < offsets[t+1], t < m -- the bytes of
+ *   pbc_hip_element_pp_pow_zn_batch on a single-base object for bases[t].  `offsets`: m + 1 values in HOST memory, read
+ *   before the call returns, offsets[0] == 0, non-decreasing (a table may serve no unit), n = offsets[m].  Units of a
+ *   "complete only" table take the complete ladder.
+ *   prod: out[i] = sum_{j<m} [zr[i m + j]] B_j (GT: prod_{j<m} B_j^zr[i m + j]), i < n: one Jacobian accumulator over the
+ *   m * length_in_bytes_Zr table entries the scalar bytes select, one inversion (GT: the plain product of the entries).
+ *   The bytes are those of m pbc_hip_element_mul_zn_batch results folded left to right with pbc_hip_element_add_batch
+ *   (GT: pbc_hip_element_pow_zn_GT_batch / pbc_hip_element_mul_GT_batch); for m = 2, 3 those of
+ *   pbc_hip_element_pow2_zn_batch / pbc_hip_element_pow3_zn_batch.  A unit whose additions meet equal or opposite
+ *   operands or whose sum is O, every unit of a set with a "complete only" table, and every unit under "hip_group_slow 1"
+ *   take the complete lane: [z_j] B_j on the complete ladder, folded with the complete affine law.
+ *   Scalars are any length_in_bytes_Zr bytes (as pbc_hip_element_pp_pow_zn_batch takes them); points come out affine, O
+ *   as zero bytes; `out` may not alias `zr`; n == 0 returns 0 and touches nothing.  The host-buffer forms are staged
+ *   through the object's own device (a unit's input record of prod: m * length_in_bytes_Zr bytes).
+ *   Errors (non-zero, pbc_hip_last_error; found BEFORE a device is looked for): null arguments, group outside 1..3,
+ *   m == 0, table bytes that overflow size_t, offsets[0] != 0, a decreasing pair of offsets.  A failed device allocation
+ *   frees everything and fails with a message. */
+typedef struct pbc_hip_element_pp_set_s pbc_hip_element_pp_set_t;
+int pbc_hip_element_pp_set_init(pbc_hip_element_pp_set_t **set, pbc_hip_pairing_t *p, int group, const uint8_t *bases, size_t m);
+int pbc_hip_element_pp_set_init_dev(pbc_hip_element_pp_set_t **set, pbc_hip_pairing_t *p, int group, const void *d_bases, size_t m, void *stream);
+void pbc_hip_element_pp_set_clear(pbc_hip_element_pp_set_t *set);
+size_t pbc_hip_element_pp_set_count(const pbc_hip_element_pp_set_t *set);
+int pbc_hip_element_pp_set_pow_zn_batch(pbc_hip_element_pp_set_t *set, uint8_t *out, const uint8_t *zr, const uint64_t *offsets);
+int pbc_hip_element_pp_set_pow_zn_batch_dev(pbc_hip_element_pp_set_t *set, void *d_out, const void *d_zr,
+                                            const uint64_t *offsets /* HOST memory */, void *stream);
+/* the check the two calls above make of their offsets (m + 1 values), for the tests: 0, or non-zero with the call's message */
+int pbc_hip_diag_element_pp_set_offsets(const uint64_t *offsets, size_t m);
+int pbc_hip_element_pp_set_prod_batch(pbc_hip_element_pp_set_t *set, uint8_t *out, const uint8_t *zr, size_t n);
+int pbc_hip_element_pp_set_prod_batch_dev(pbc_hip_element_pp_set_t *set, void *d_out, const void *d_zr, size_t n, void *stream);
 /* pairing->finalpow (include/pbc_pairing.h:41; a_finalpow ecc/a_param.c:1420-1429, cc_finalpow ecc/d_param.c:566-568,
  * f_finalpow ecc/f_param.c:285-287, g_finalpow ecc/g_param.c:1162-1164, e_finalpow ecc/e_param.c:828-830; its callers
  * are gt_random / gt_from_hash, ecc/pairing.c:121,127): out[i] = in[i]^((q^k - 1)/r), the final exponentiation alone,

@@ -148,6 +148,17 @@ def lib():
         L.pbc_hip_diag_pp_set_plan.argtypes = [vp, vp, sz, vp, sz]
         L.pbc_hip_pairing_pp_set_prod_batch.argtypes = [vp, vp, vp, sz]
         L.pbc_hip_pairing_pp_set_prod_batch_dev.argtypes = [vp, vp, vp, sz, vp]
+        L.pbc_hip_element_pp_set_init.argtypes = [ctypes.POINTER(vp), vp, ci, vp, sz]
+        L.pbc_hip_element_pp_set_init_dev.argtypes = [ctypes.POINTER(vp), vp, ci, vp, sz, vp]
+        L.pbc_hip_element_pp_set_clear.argtypes = [vp]
+        L.pbc_hip_element_pp_set_clear.restype = None
+        L.pbc_hip_element_pp_set_count.argtypes = [vp]
+        L.pbc_hip_element_pp_set_count.restype = sz
+        L.pbc_hip_element_pp_set_pow_zn_batch.argtypes = [vp, vp, vp, vp]
+        L.pbc_hip_element_pp_set_pow_zn_batch_dev.argtypes = [vp, vp, vp, vp, vp]
+        L.pbc_hip_element_pp_set_prod_batch.argtypes = [vp, vp, vp, sz]
+        L.pbc_hip_diag_element_pp_set_offsets.argtypes = [vp, sz]
+        L.pbc_hip_element_pp_set_prod_batch_dev.argtypes = [vp, vp, vp, sz, vp]
         L.pbc_hip_element_membership_batch.argtypes = [vp, ci, vp, vp, sz]
         L.pbc_hip_element_membership_batch_dev.argtypes = [vp, ci, vp, vp, sz, vp]
         L.pbc_hip_element_mul_mpz_batch.argtypes = [vp, ci, vp, vp, vp, sz, sz]
@@ -192,6 +203,9 @@ EXPORTS = (
     "pbc_hip_pairing_pp_set_init", "pbc_hip_pairing_pp_set_init_dev", "pbc_hip_pairing_pp_set_clear", "pbc_hip_pairing_pp_set_count",
     "pbc_hip_pairing_pp_set_apply_batch", "pbc_hip_pairing_pp_set_apply_batch_dev", "pbc_hip_diag_pp_set_plan",
     "pbc_hip_pairing_pp_set_prod_batch", "pbc_hip_pairing_pp_set_prod_batch_dev",
+    "pbc_hip_element_pp_set_init", "pbc_hip_element_pp_set_init_dev", "pbc_hip_element_pp_set_clear", "pbc_hip_element_pp_set_count",
+    "pbc_hip_element_pp_set_pow_zn_batch", "pbc_hip_element_pp_set_pow_zn_batch_dev",
+    "pbc_hip_element_pp_set_prod_batch", "pbc_hip_element_pp_set_prod_batch_dev", "pbc_hip_diag_element_pp_set_offsets",
     "pbc_hip_element_membership_batch", "pbc_hip_element_membership_batch_dev",
     "pbc_hip_element_mul_mpz_batch", "pbc_hip_element_mul_mpz_batch_dev", "pbc_hip_diag_mpz_digits",
 )
@@ -732,6 +746,14 @@ class Pairing:
         """Mirror of element_pp_init: fixed-base powers of one element of G1 / G2 (group 1, 2) or GT (group 3)."""
         return ElementPP(self, group, rec)
 
+    def element_pp_set_init(self, group, bases):
+        """A set of fixed-base tables: one element_pp table per row of ``bases`` (m records of the group), built in one launch."""
+        return ElementPPSet(self, group, bases=bases)
+
+    def element_pp_set_init_dev(self, group, d_bases, m, stream=0):
+        """The same from m device-resident records, enqueued on ``stream`` (asynchronous)."""
+        return ElementPPSet(self, group, d_bases=d_bases, m=m, stream=stream)
+
     # ---- preprocessed pairings (pairing_pp_init / pairing_pp_apply) ----------------------
     def finalpow(self, a):
         """pairing->finalpow over (n, lenGT) records of GT's underlying field"""
@@ -929,6 +951,85 @@ class ElementPP:
         if getattr(self, "_h", None):
             try:
                 lib().pbc_hip_element_pp_clear(self._h)
+            except TypeError:          # interpreter shutdown: the module's globals are gone
+                pass
+            self._h = None
+
+    __del__ = clear
+
+
+class ElementPPSet:
+    """m element_pp tables of one group (include/pbc_hip.h pbc_hip_element_pp_set_t): a segmented element_pp_pow_zn, and
+    multi-base powers whose bases are the set's."""
+
+    def __init__(self, pairing, group, bases=None, d_bases=None, m=None, stream=0):
+        import numpy as np
+        self.pairing, self.group = pairing, group
+        self._h = ctypes.c_void_p()
+        self.length = pairing._group_len(group) if group in (1, 2, 3) else 1      # (a bad group is the library's to refuse)
+        if bases is not None:
+            bases = np.ascontiguousarray(bases, dtype=np.uint8)
+            if bases.size % self.length:
+                raise ValueError("bases must hold whole records of the group")
+            rc = lib().pbc_hip_element_pp_set_init(ctypes.byref(self._h), pairing._h, group, _np_ptr(bases) if bases.size else 1,
+                                                   bases.size // self.length)
+        else:
+            rc = lib().pbc_hip_element_pp_set_init_dev(ctypes.byref(self._h), pairing._h, group, d_bases, m, stream)
+        if rc:
+            self._h = None
+            raise PbcHipError("element_pp_set_init: " + _err())
+        self.m = lib().pbc_hip_element_pp_set_count(self._h)
+
+    def count(self):
+        return lib().pbc_hip_element_pp_set_count(self._h)
+
+    def _offsets(self, offsets):
+        import numpy as np
+        off = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
+        if off.size != self.m + 1:
+            raise ValueError("offsets needs m + 1 = %d values" % (self.m + 1))
+        return off
+
+    def pow_zn(self, zr, offsets):
+        """out[u] = [zr[u]] B_t (GT: B_t^zr[u]) for offsets[t] <= u < offsets[t+1]: np.uint8 of shape (offsets[-1], record length)"""
+        import numpy as np
+        zr = np.ascontiguousarray(zr, dtype=np.uint8)
+        off = self._offsets(offsets)
+        n = int(off[-1])
+        if zr.size != n * self.pairing.length_in_bytes_Zr:
+            raise ValueError("zr does not hold offsets[-1] = %d scalars" % n)
+        out = np.empty((n, self.length), np.uint8)
+        if lib().pbc_hip_element_pp_set_pow_zn_batch(self._h, _np_ptr(out) if n else 1, _np_ptr(zr) if n else 1, _np_ptr(off)):
+            raise PbcHipError("element_pp_set_pow_zn: " + _err())
+        return out
+
+    def pow_zn_dev(self, d_out, d_zr, offsets, stream=0):
+        """the same on device pointers, enqueued on ``stream``; ``offsets`` is a host array and may be reused on return"""
+        off = self._offsets(offsets)
+        if lib().pbc_hip_element_pp_set_pow_zn_batch_dev(self._h, d_out, d_zr, _np_ptr(off), stream):
+            raise PbcHipError("element_pp_set_pow_zn_dev: " + _err())
+
+    def prod(self, zr):
+        """out[i] = sum over j < m of [zr[i*m + j]] B_j (GT: the product of the powers); zr holds n*m scalars"""
+        import numpy as np
+        zr = np.ascontiguousarray(zr, dtype=np.uint8)
+        per = self.m * self.pairing.length_in_bytes_Zr
+        if zr.size % per:
+            raise ValueError("zr must hold n * m scalars")
+        n = zr.size // per
+        out = np.empty((n, self.length), np.uint8)
+        if lib().pbc_hip_element_pp_set_prod_batch(self._h, _np_ptr(out) if n else 1, _np_ptr(zr) if n else 1, n):
+            raise PbcHipError("element_pp_set_prod: " + _err())
+        return out
+
+    def prod_dev(self, d_out, d_zr, n, stream=0):
+        if lib().pbc_hip_element_pp_set_prod_batch_dev(self._h, d_out, d_zr, n, stream):
+            raise PbcHipError("element_pp_set_prod_dev: " + _err())
+
+    def clear(self):
+        if getattr(self, "_h", None):
+            try:
+                lib().pbc_hip_element_pp_set_clear(self._h)
             except TypeError:          # interpreter shutdown: the module's globals are gone
                 pass
             self._h = None
