@@ -15,8 +15,8 @@
 //     Z2) is affine, the odd multiples follow by mixed additions there (additions do not involve the curve coefficient)
 //     and go back to E by Z <- Z Z2; one batched inversion makes them affine.  Two inversions per scalar multiplication
 //     (safegcd) against the ~190 of the reference's affine ladder.
-//   * The step formulas are the incomplete ones of the Miller loop (pairing_al.cuh double_step / add_step without the
-//     line): an addition that meets R = +-T or R = O has H = 0 and leaves Z = 0 for good.  The lane routine reports
+//   * The step formulas are the incomplete Jacobian ones of the word-form Miller loop (pairing_a.cuh a_double_step /
+//     a_add_step without the line, in limb form): an addition that meets R = +-T or R = O has H = 0 and leaves Z = 0 for good.  The lane routine reports
 //     "Z = 0 at the end" (the true result O, a point of small order, an exceptional scalar) and the caller runs the
 //     complete word-form routine of group_ops.cuh (ec_mul_lane) for those lanes only -- a second, nearly empty launch.
 //   * GT: elements of norm 1 (every pairing value, every power and product of them) are powered with the Lucas ladder of
@@ -53,7 +53,9 @@ struct GAL {
   }
 
   // V <- 2V on y^2 = x^3 + x.  V = (X, Y) in registers (almost normalised, B <= 14), Z and Z^2 in their LDS slots (P-class).
-  // The point part of AL::double_step: 3 products + 6 squarings.
+  // The point part of the JACOBIAN doubling step (pairing_a.cuh a_double_step in limb form): 3 products + 6 squarings.  (The
+  // Miller loop of pairing_al.cuh has moved to x = X / Z, y = Y / Z^2, where a doubling is 2 products + 5 squarings; the
+  // ladders keep the Jacobian point.)
   static PBC_DEV void ec_dbl(jacl &V) {
     el XX, YY, M, t0, t1, Z3, S1, W;
     A::sqr(XX, V.X);
@@ -85,7 +87,7 @@ struct GAL {
     A::subk(t0, t0, t1, K12);          // u 4, B 13.1
     A::norm(V.Y, t0);                  // Y3 = M (S - X3) - 8Y^4
   }
-  // V <- V + (x2, y2), mixed.  The point part of AL::add_step: 8 products + 3 squarings.  x2, y2: limbs <= 2^29 + 6, B <= 14.
+  // V <- V + (x2, y2), mixed.  The point part of the Jacobian addition step (a_add_step): 8 products + 3 squarings.  x2, y2: limbs <= 2^29 + 6, B <= 14.
   // Incomplete: V = +-(x2, y2) or V = O give H = 0 and Z3 = 0, which later steps keep.
   static PBC_DEV void ec_madd(jacl &V, const el &x2, const el &y2) {
     el H, R, Z3, HH, HHH, t0, t1;

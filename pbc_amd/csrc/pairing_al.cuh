@@ -1,13 +1,20 @@
 // pairing_al.cuh -- Type A (a.param: 512-bit q, 16 words) with F_q elements kept in 29-bit LIMB form.
 //
 // element_pairing (a_pairing_proj + a_tateexp, ecc/a_param.c:1053-1198, :285-303) and pairing_pp_apply (:317-360) with
-// the Jacobian Miller steps and the Lucas-sequence final exponentiation of pairing_a.cuh (a_double_step, a_add_step,
-// a_final_exp: the word-form routines the other type a kernels use) -- but an element is L = 18 limbs of 29 bits
-// from the moment it is loaded until it is stored.  The word-form kernel converts both operands of every product into
-// limbs and the result back into words with a conditional subtraction: 150 of the 900 instructions of a product
-// (measured by a what-if build: +14 % pairings/s without them, profiles/r02_notes.md).  The multiply-add pipe takes a
-// v_mad_u64_u32 every 4.58 cycles per SIMD and any other VALU instruction ~2.5 (tools/mac_chain_probe.hip); this
-// kernel's 2.15 M multiply-adds + 0.77 M other instructions per pairing run at 92 % of that pipe-time.
+// the Lucas-sequence final exponentiation of pairing_a.cuh (a_final_exp: the word-form routine the other type a kernels
+// use) -- but an element is L = 18 limbs of 29 bits from the moment it is loaded until it is stored.  The word-form
+// kernel converts both operands of every product into limbs and the result back into words with a conditional
+// subtraction: 150 of the 900 instructions of a product (measured by a what-if build: +14 % pairings/s without them,
+// profiles/r02_notes.md).  The multiply-add pipe takes a v_mad_u64_u32 every 4.58 cycles per SIMD and any other VALU
+// instruction ~2.5 (tools/mac_chain_probe.hip); the multiply-adds are five sixths of this kernel's time, so the Miller
+// loop is built to execute few of them: 2.02 M per pairing (profiles/executed_macs.json).
+//
+// The Miller steps are NOT the Jacobian ones of pairing_a.cuh (a_double_step, a_add_step; pairing_aw.cuh and the G1
+// ladders of group_al.cuh keep those).  The running point is V = (X, Y, Z) with x = X / Z, y = Y / Z^2 (weights 1, 2):
+// on y^2 = x^3 + x the doubled point is X3 = (X^2 - Z^2)^2, Z3 = 4 Y^2, and with y^2 replaced by x^3 + x the real part of
+// the tangent at phi(Q) collapses to T Qx + X (X^2 - Z^2), one two-term sum: 5 products + 5 squarings + 1 two-term sum
+// for point and line where the Jacobian step takes 7 + 6 (double_step below).  The lines differ from the Jacobian ones
+// by factors in F_q^*, which the final exponentiation removes: the GT bytes are the same.
 //
 // Redundant representation.  R = 2^522 and q < 2^512, so there are ten bits of slack: a value is any 18 limbs whose
 // sum is congruent to it; a Montgomery product of operands below 16 q comes out below 1.25 q ("P-class": limbs
@@ -23,12 +30,14 @@
 // corresponding limb of b (borrowed form: limb_i(c q) + D 2^29 - D); the host precomputes the five K it needs.
 //
 // Calling convention of the out-of-line products.  An operand is 18 VGPRs and the ABI passes 31: the first operand
-// travels in registers, the second as 12 registers + 6 words of LDS.  The Miller accumulator f and the coordinates
-// Z, Z^2 of the running point live in LDS for the whole loop (four slots): 72 registers less in the point arithmetic
-// (a value that lives across a call must sit in one of the ABI's 108 callee-saved VGPRs or be spilled); Q sits in the
-// lane's private memory.  LDS per lane: 4 x 18 + 6 words = 312 B -> 39 KB per 128-lane workgroup, four workgroups
-// (two waves per SIMD) per CU.  Three product bodies in all (product, square, two-term sum against f): the Miller loop's
-// code is 31 KB; variants with fused f^2 / f * line bodies (64 KB per iteration) ran 3 % slower (profiles/r02_notes.md).
+// travels in registers, the second as 12 registers + 6 words of LDS.  The Miller accumulator f and the coordinate Z
+// of the running point live in LDS for the whole loop (slots 0 - 2 of four); slot 3 is scratch: within a doubling
+// step it parks X, and once Z is dead slot 2 takes T, so that T Qx + X N is a two-term sum against the slot pair
+// (2, 3) exactly as f's are against the pair (0, 1).  (A value that lives across a call must sit in one of the ABI's
+// 108 callee-saved VGPRs or be spilled.)  Q sits in the lane's private memory.  LDS per lane: 4 x 18 + 6 words = 312 B
+// -> 39 KB per 128-lane workgroup, four workgroups (two waves per SIMD) per CU.  Three product bodies in all (product,
+// square, two-term sum against a slot pair): the Miller loop's code stays within the instruction cache; variants with
+// fused f^2 / f * line bodies (64 KB per iteration) ran 3 % slower (profiles/r02_notes.md).
 #pragma once
 #include "pairing_a.cuh"
 
@@ -62,7 +71,9 @@ struct AL {
   typedef fl<N> el;
   typedef uint32_t vL __attribute__((ext_vector_type(L)));
   typedef uint32_t vLo __attribute__((ext_vector_type(12)));
-  enum { SLOT_FX = 0, SLOT_FY = 1, SLOT_Z = 2, SLOT_ZZ = 3 };
+  // (SLOT_ZZ: Z^2 of the Jacobian ladders of group_al.cuh; the Miller loop below does not carry Z^2 and uses the slot
+  // as SLOT_TMP, the partner of SLOT_Z in the line's two-term sum)
+  enum { SLOT_FX = 0, SLOT_FY = 1, SLOT_Z = 2, SLOT_ZZ = 3, SLOT_TMP = 3 };
   enum { K2 = 0, K4 = 1, K8 = 2, K12 = 3, K16 = 4 };   // AConst::ksub: (c, D) = (2, 1), (4, 2), (8, 4), (12, 2), (16, 2)
 
   // ---- host mirror only: worst-case bound tracker ----------------------------------------------------------------
@@ -241,8 +252,9 @@ struct AL {
     AL_HS(hs_au = r.hs_u; hs_aB = r.hs_B;)
     return to_v(r);
   }
-  // fx p + (+-fy) q with f read from its LDS slots, one reduction
-  static __device__ __noinline__ vL fsop_fn(vL vp, vLo qlo, int neg) {
+  // fx p + (+-fy) q with (fx, fy) read from the LDS slots (base, base + 1), one reduction: base = SLOT_FX is f, base =
+  // SLOT_Z the pair a doubling step parks there for its line
+  static __device__ __noinline__ vL fsop_fn(vL vp, vLo qlo, int neg, int base) {
     el fx, fy, p, q, r;
     from_v(p, vp);
     AL_HS(p.hs_u = hs_au; p.hs_B = hs_aB; q.hs_u = hs_bu; q.hs_B = hs_bB;)
@@ -250,8 +262,8 @@ struct AL {
     for (int i = 0; i < 12; i++) q.l[i] = qlo[i];
 #pragma unroll
     for (int i = 12; i < L; i++) q.l[i] = lds_hi(i - 12);
-    lds_get(fx, SLOT_FX);
-    lds_get(fy, SLOT_FY);
+    lds_get(fx, base);
+    lds_get(fy, base + 1);
     if (neg) {
       negk(fy, fy, K2);                // u 2, B 2
       norm(fy, fy);
@@ -260,14 +272,14 @@ struct AL {
     AL_HS(hs_au = r.hs_u; hs_aB = r.hs_B;)
     return to_v(r);
   }
-  static PBC_DEV void fsop(el &r, const el &p, const el &q, int neg) {
+  static PBC_DEV void fsop(el &r, const el &p, const el &q, int neg, int base = SLOT_FX) {
     vLo lo;
 #pragma unroll
     for (int i = 0; i < 12; i++) lo[i] = q.l[i];
 #pragma unroll
     for (int i = 12; i < L; i++) lds_hi(i - 12) = q.l[i];
     AL_HS(hs_au = p.hs_u; hs_aB = p.hs_B; hs_bu = q.hs_u; hs_bB = q.hs_B;)
-    from_v(r, fsop_fn(to_v(p), lo, neg));
+    from_v(r, fsop_fn(to_v(p), lo, neg, base));
     AL_HS(r.hs_u = hs_au; r.hs_B = hs_aB;)
   }
 
@@ -344,100 +356,105 @@ struct AL {
     }
   };
 
-  // The point V = (X, Y, Z) of the Miller loop: X, Y in registers (almost normalised, B <= 14), Z and Z^2 in their
-  // LDS slots (P-class); Q = (Qx, Qy) in the lane's private memory as 2 x 18 canonical limbs.
+  // The point V = (X, Y, Z) of the Miller loop, x = X / Z, y = Y / Z^2: X, Y in registers (P-class after a doubling
+  // step; almost normalised, B <= 3.5 after the addition step), Z in its LDS slot (almost normalised, B <= 4.1);
+  // Q = (Qx, Qy) in the lane's private memory as 2 x 18 canonical limbs.  (The ladders of group_al.cuh keep a Jacobian
+  // point in the same struct, with Z^2 in the fourth slot.)
   struct jacl {
     el X, Y;
   };
 
-  // One doubling step: f <- f^2 l_{V,V}(phi(Q)), V <- 2V.  Same line as a_double_step (pairing_a.cuh):
-  //     re = M (ZZ Qx + X) - 2 Y^2,  im = (2YZ) ZZ Qy,  M = 3X^2 + Z^4.
-  // Where the word-form step trades products for squarings, this one takes products: a squaring of a sum needs the
-  // sum normalised first, which costs more than the squaring saves.  9 M + 6 S + 2 two-term sums per step.
+  // One doubling step: f <- f^2 l_{V,V}(phi(Q)), V <- 2V, on y^2 = x^3 + x with x = X / Z, y = Y / Z^2.  With A = X^2,
+  // B = Y^2, C = Z^2, N = A - C, P = A + C:
+  //     x(2V) = (x^2 - 1)^2 / 4y^2                 ->  X3 = N^2,  Z3 = 4B
+  //     y(2V) = (x^2 - 1)(x^4 + 6x^2 + 1) / 8y^3   ->  Y3 = (2P^2 - X3) (2Y N)
+  // and the tangent at phi(Q) = (-Qx, i Qy), scaled by 2y Z^3 in F_q^*, with 2y^2 Z^3 = 2X (A + C) from the curve:
+  //     re = T Qx + X N,  T = (3A + C) Z;          im = (2YZ) Qy.
+  // re is ONE two-term sum against the slot pair (SLOT_Z, SLOT_TMP): X is parked in SLOT_TMP as soon as A exists, and
+  // T takes Z's slot once 2YZ exists -- Z is dead from there on, Z3 is written at the end of the step.
+  // 7 M + 5 S + 3 two-term sums per step, f^2 and f l included (the Jacobian step: 9 M + 6 S + 2).
   static PBC_DEV void double_step(jacl &V, const QPriv &Q) {
-    el XX, YY, M, t0, t1, lx, ly, Z3, S1, W;
+    el A, C, Nn, Pp, t0, t1, lx, ly;
     pbc_fair_tick<PBC_A_FAIR_BIT>();
     fsqr();
-    sqr(XX, V.X);
-    lds_get(t0, SLOT_ZZ);
-    sqr(t0, t0);                       // Z^4
-    shl<1>(M, XX);
-    add(M, M, XX);
-    add(M, M, t0);                     // u 4, B 5
-    norm(M, M);
-    sqr(YY, V.Y);
-    Q.get(t1, 0);
-    muls(t0, t1, SLOT_ZZ);             // ZZ Qx
-    add(t0, t0, V.X);                  // u 2, B 10.5
-    mul(lx, M, t0);                    // P
-    shl<1>(t1, YY);                    // u 2, B 3
-    subk(lx, lx, t1, K4);              // u 4, B 5.5
-    norm(lx, lx);
+    sqr(A, V.X);
+    lds_put(SLOT_TMP, V.X);            //                      (X lives in its slot until re)
+    lds_get(t0, SLOT_Z);
+    sqr(C, t0);                        // B 1.04
+    subk(Nn, A, C, K2);                // u 3, B 3.1
+    norm(Nn, Nn);
+    add(t1, A, C);                     // u 2, B 2.1
+    norm(Pp, t1);
+    shl<1>(t0, A);
+    add(t0, t0, t1);                   // 3A + C: u 4, B 4.1
+    norm(t0, t0);
+    muls(t0, t0, SLOT_Z);              // T: P
     shl<1>(t1, V.Y);                   // u 2
-    muls(Z3, t1, SLOT_Z);              // Z3 = 2YZ
-    muls(t1, Z3, SLOT_ZZ);             //                      (Z, ZZ dead)
-    lds_put(SLOT_Z, Z3);
-    sqr(Z3, Z3);
-    lds_put(SLOT_ZZ, Z3);
-    Q.get(Z3, 1);
-    mul(ly, t1, Z3);                   // im = Z3 ZZ Qy
+    muls(t1, t1, SLOT_Z);              // 2YZ                  (Z dead)
+    lds_put(SLOT_Z, t0);
+    Q.get(t0, 1);
+    mul(ly, t1, t0);                   // im
+    Q.get(t0, 0);
+    fsop(lx, t0, Nn, 0, SLOT_Z);       // re = T Qx + X N: four normalised operands, column sum 2
     fmul(lx, ly);
-    shl<1>(t1, V.X);                   // u 2
-    mul(S1, YY, t1);                   // 2XY^2
-    sqr(t0, M);
-    shl<2>(t1, S1);                    // 8XY^2: u 4, B 6
-    subk(t0, t0, t1, K8);              // u 6, B 9.5
-    norm(V.X, t0);                     // X3 = M^2 - 2S
-    shl<1>(t1, S1);                    // S = 4XY^2: u 2, B 3
-    subk(W, t1, V.X, K12);             // S - X3: u 5, B 15
-    norm(W, W);
-    mul(t0, M, W);
-    sqr(t1, YY);                       // Y^4
-    shl<3>(t1, t1);                    // u 8, B 12
-    norm(t1, t1);
-    subk(t0, t0, t1, K12);             // u 4, B 13.1
-    norm(V.Y, t0);                     // Y3 = M (S - X3) - 8Y^4
+    sqr(V.X, Nn);                      // X3: P
+    sqr(t0, Pp);
+    shl<1>(t0, t0);                    // u 2, B 2.1
+    subk(t0, t0, V.X, K2);             // u 4, B 4.1
+    norm(t0, t0);                      // E = 2P^2 - X3
+    shl<1>(t1, V.Y);                   // u 2
+    mul(t1, t1, Nn);                   // F = 2Y N
+    sqr(C, V.Y);
+    shl<2>(C, C);                      // u 4, B 4.1
+    norm(C, C);
+    lds_put(SLOT_Z, C);                // Z3 = 4B
+    mul(V.Y, t0, t1);                  // Y3 = E F: P
   }
 
-  // Mixed addition step (a_add_step, pairing_a.cuh): runs once per pairing, so every difference is normalised at once.
+  // Mixed addition step V <- V + (x2, y2), f <- f l_{V,(x2,y2)}(phi(Q)) in the same coordinates: the chord has slope
+  // R / W with H = x2 Z - X, R = y2 Z^2 - Y, W = Z H; scaled by W and with G = W H = Z H^2:
+  //     re = R (Qx + x2) - W y2,  im = W Qy
+  //     X3 = R^2 - (X + x2 Z) G,  Y3 = R W (X G - X3) - Y G^2,  Z3 = W^2.
+  // Runs once per pairing, so every difference is normalised at once.  V comes from a doubling step (X, Y: P-class);
+  // x2, y2: almost normalised, B <= 2.
   static PBC_DEV void add_step(jacl &V, const el &x2, const el &y2, const QPriv &Q) {
-    el H, R, Z3, HH, HHH, t0, t1, lx, ly;
-    muls(t0, x2, SLOT_ZZ);
-    subk(H, t0, V.X, K16);
-    norm(H, H);                        // B 17.5
-    lds_get(t0, SLOT_Z);
-    muls(t0, t0, SLOT_ZZ);
+    el H, R, W, G, S, Z, t0, t1, lx, ly;
+    lds_get(Z, SLOT_Z);
+    mul(t0, x2, Z);                    // x2 Z
+    add(S, t0, V.X);                   // u 2, B 3
+    norm(S, S);
+    subk(H, t0, V.X, K2);
+    norm(H, H);                        // B 3.5
+    sqr(t0, Z);
     mul(t0, y2, t0);
-    subk(R, t0, V.Y, K16);
-    norm(R, R);                        // B 17.5
-    muls(Z3, H, SLOT_Z);
+    subk(R, t0, V.Y, K2);
+    norm(R, R);                        // B 3.5
+    mul(W, Z, H);
+    mul(G, W, H);
     Q.get(t0, 0);
     add(t0, t0, x2);                   // u 2
     mul(lx, R, t0);
-    mul(t0, Z3, y2);
+    mul(t0, W, y2);
     subk(lx, lx, t0, K2);
     norm(lx, lx);                      // B 3.5
     Q.get(t0, 1);
-    mul(ly, Z3, t0);
-    sqr(HH, H);
-    mul(HHH, HH, H);
-    mul(t0, V.X, HH);                  // X1 H^2
+    mul(ly, W, t0);
     sqr(t1, R);
-    subk(t1, t1, HHH, K2);
-    norm(t1, t1);                      // B 3.5
-    shl<1>(HH, t0);                    // u 2, B 3
-    subk(t1, t1, HH, K4);
-    norm(t1, t1);                      // X3 = R^2 - H^3 - 2 X1 H^2, B 7.5
-    subk(t0, t0, t1, K16);
-    norm(t0, t0);                      // B 17.5
-    mul(t0, R, t0);
-    mul(HHH, V.Y, HHH);
-    subk(t0, t0, HHH, K2);
-    norm(V.Y, t0);                     // Y3 = R (X1 H^2 - X3) - Y1 H^3, B 3.5
+    mul(t0, S, G);
+    subk(t1, t1, t0, K2);
+    norm(t1, t1);                      // X3 = R^2 - (X + x2 Z) G, B 3.5
+    mul(t0, V.X, G);
+    subk(t0, t0, t1, K4);              // (X3 is almost normalised: K4's limbs dominate it)
+    norm(t0, t0);                      // X G - X3, B 5.5
+    mul(S, R, W);
+    mul(t0, S, t0);
+    sqr(G, G);
+    mul(G, V.Y, G);
+    subk(t0, t0, G, K2);
+    norm(V.Y, t0);                     // Y3 = R W (X G - X3) - Y G^2, B 3.5
     V.X = t1;
-    lds_put(SLOT_Z, Z3);
-    sqr(Z3, Z3);
-    lds_put(SLOT_ZZ, Z3);
+    sqr(W, W);
+    lds_put(SLOT_Z, W);                // Z3: P
     fmul(lx, ly);
   }
 
@@ -614,7 +631,6 @@ struct AL {
       fp_set<N>(Px, fpk<N>().one);
       to_el(q, Px);
       lds_put(SLOT_Z, q);
-      lds_put(SLOT_ZZ, q);
       lds_put(SLOT_FX, q);
 #pragma unroll
       for (int i = 0; i < L; i++) q.l[i] = 0;

@@ -12,9 +12,11 @@
 // a b / R + (multiple of q); carry passes (DPP, wave-uniform loop on a ballot) bring the limbs below 2^29.  Seven
 // vector instructions per step; about 1 300 cycles per product against 5 900 for the 648 multiply-adds of a lane-local
 // product at one wave per SIMD.
-// The ALGORITHM is AL<N>'s, operation for operation (double_step, add_step, final_exp: same sums, same borrowed
-// constants, same normalisations, hence the same bounds -- in the host mirror an element IS an AL<N>::el and carries
-// AL's worst-case tracker through these routines), so the two paths agree bit for bit on every input, the invalid
+// The final exponentiation is AL<N>'s, operation for operation (same sums, same borrowed constants, same
+// normalisations, hence the same bounds -- in the host mirror an element IS an AL<N>::el and carries AL's worst-case
+// tracker through these routines).  The Miller steps (double_step, add_step below) are the JACOBIAN ones AL<N> had
+// before it moved to weight-(1, 2) coordinates (pairing_al.cuh): the two paths' Miller values now differ by factors
+// in F_q^*, which the final exponentiation removes, so they still agree bit for bit on every input, the invalid
 // ones included; the one inversion runs AL's divsteps routine on lane 0 (a Fermat ladder on the wave's products,
 // `invert`, is kept for reference: 0.32 against 0.14 ms).
 // Boundaries (bytes <-> limbs, validity, the final halvings) run the word-form routines on lane 0 through LDS.
@@ -542,7 +544,7 @@ struct AW {
     const W nfy = norm(negk(s.fy, K2));
     sop2x2(s.fx, s.fy, s.fx, lx, nfy, ly, s.fx, ly, s.fy, lx);
   }
-  // AL::double_step, its 19 products in four rounds of up to four independent ones and the two two-term sums of f l
+  // The Jacobian doubling step (pairing_a.cuh a_double_step in limb form), its 19 products in four rounds of up to four independent ones and the two two-term sums of f l
   PBC_DEV void double_step(state &s) {
     W XX, Z4, YY, t0, t1, lx, ly, Z3, S1, MM, Y4, nfx, nfy, ZZn, u;
     {
@@ -570,7 +572,7 @@ struct AW {
     t1 = norm(shl<3>(Y4));
     s.Y = norm(subk(t0, t1, K12));
   }
-  PBC_DEV void add_step(state &s, const W &x2, const W &y2) {   // AL::add_step
+  PBC_DEV void add_step(state &s, const W &x2, const W &y2) {   // the Jacobian mixed addition step (a_add_step in limb form)
     if constexpr (kDigits) {
       // (an order with hundreds of non-zero digits: the same products -- the same operand classes, the same borrowed constants --
       // in five rounds of up to four independent ones instead of one after the other)
@@ -667,7 +669,7 @@ struct AW {
       s.X = X3; s.Z = Z3; s.ZZ = ZZn;
       plx = lx; ply = r[1]; pending = true;
       const int dig = i > 0 ? a1_digit(i) : 0;
-      if (dig) {                                               // AL::add_step; its first round takes the waiting line along
+      if (dig) {                                               // the Jacobian addition step; its first round takes the waiting line along
         const W x2 = Px, y2 = dig < 0 ? nPy : Py;
         W a, b;
         {
