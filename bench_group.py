@@ -7,6 +7,8 @@ A step:
   *-g1-mul / *-g2-mul   one element_mul_zn launch: n points x n random scalars below r
   *-gt-pow              one element_pow_zn launch on n pairing values
   *-hash-g1             one element_from_hash launch on n 32-byte digests
+  *-gt-invert / *-gt-div  one element_invert / element_div launch on n pairing values (the lanes store conjugates)
+  d-g2-cmp / f-g2-cmp   one element_cmp launch on n pairs of twist points (the coset compare: a - b, a ladder, a test for O)
   *-g1-pp / *-gt-pp     one element_pp_pow_zn launch: n scalars against ONE preprocessed base (element_pp_init outside the clock)
   a-bls-verify          the flow of example/bls.c:64-117 for n signatures as a batch, device-resident throughout: hash the n
                         digests, scale hash and signature of message j by a random r_j (resp. -r_j), and check the products
@@ -45,16 +47,22 @@ for _t, _p, _fx in (("a", "a", "a_chain1024.vec"), ("d", "d159", "d_chain256.vec
     GROUP_WORKLOADS[_t + "-zr-inv"] = (_p, _fx, "zrinv", 20)
     GROUP_WORKLOADS[_t + "-g1-pow2"] = (_p, _fx, "g1pow2", 18 if _t == "a" else 17)
     GROUP_WORKLOADS[_t + "-gt-pow2"] = (_p, _fx, "gtpow2", 18 if _t == "a" else 16)
+    GROUP_WORKLOADS[_t + "-gt-invert"] = (_p, _fx, "gtinvert", 18)
+    GROUP_WORKLOADS[_t + "-gt-div"] = (_p, _fx, "gtdiv", 18)
+    if _t != "a":                      # (the symmetric types compare coordinates)
+        GROUP_WORKLOADS[_t + "-g2-cmp"] = (_p, _fx, "g2cmp", 18)
 GROUP_WORKLOADS["a-bls-verify"] = ("a", "a_chain1024.vec", "blsverify", 17)
 
 DESC = {"g1mul": "element_mul_zn on G1", "g2mul": "element_mul_zn on G2 (the twist)", "gtpow": "element_pow_zn on GT",
         "hashg1": "element_from_hash on G1 (32-byte digests)", "g1pp": "element_pp_pow_zn on G1 (fixed base)",
         "gtpp": "element_pp_pow_zn on GT (fixed base)", "decompress": "element_from_bytes_compressed on G1",
         "compress": "element_to_bytes_compressed on G1", "g1add": "element_add on G1", "zrinv": "element_invert on Zr",
-        "g1pow2": "element_pow2_zn on G1", "gtpow2": "element_pow2_zn on GT", "blsverify": "BLS batch verification (hash, 2 x mul_zn, 16-term products)"}
+        "g1pow2": "element_pow2_zn on G1", "gtpow2": "element_pow2_zn on GT",
+        "gtinvert": "element_invert on GT", "gtdiv": "element_div on GT", "g2cmp": "element_cmp on G2 (the twist: coset compare)", "blsverify": "BLS batch verification (hash, 2 x mul_zn, 16-term products)"}
 UNIT = {"g1mul": "scalar multiplications/s", "g2mul": "scalar multiplications/s", "gtpow": "powers/s", "hashg1": "hashes/s",
         "g1pp": "scalar multiplications/s", "gtpp": "powers/s", "decompress": "points/s", "compress": "points/s", "blsverify": "signatures/s",
-        "g1add": "additions/s", "zrinv": "inversions/s", "g1pow2": "double scalar multiplications/s", "gtpow2": "double powers/s"}
+        "g1add": "additions/s", "zrinv": "inversions/s", "g1pow2": "double scalar multiplications/s", "gtpow2": "double powers/s",
+        "gtinvert": "inversions/s", "gtdiv": "divisions/s", "g2cmp": "comparisons/s"}
 
 
 def param_int(text, key):
@@ -121,12 +129,36 @@ def reference_model(text, op, nlimb):
         if op == "g1pow2":
             return b * 4 * fmul[d] + (0.75 * b + 1) * 3 * fmul[d], b + 0.75 * b + 1
         return (b + 0.75 * b + 1) * fmul[d], 0
+    if op in ("gtinvert", "gtdiv"):
+        # fi_invert / fq_invert (arith/fieldi.c, fieldquadratic.c): x^2, y^2 (times nqr), the inversion of the norm in the
+        # half-degree field, two products by it; type f: GT is a polymod over F_q^2 and polymod_invert is ONE extended
+        # Euclid (no priced product).  element_div = invert + one product in GT.
+        half = {"a": 1, "d": 3, "f": 0}[typ]
+        inv_prods = 0 if not half else (4 if half == 1 else 5 * fmul[half])
+        return inv_prods + (fmul[ext[2]] if op == "gtdiv" else 0), 1
+    if op == "g2cmp":
+        # curve_cmp (ecc/curve.c:375-391): element_div (one affine addition) and element_pow_mpz by quotient_cmp
+        d = ext[1]
+        cs, cm = pow_ops(quotient_cmp_bits(text))
+        return 3 * fmul[d] + cs * 4 * fmul[d] + cm * 3 * fmul[d], 1 + cs + cm
     rows = b // 5 + 1                  # element_pow_base_table (arith/field.c:286-323): one multiplication per 5-bit row
     if op == "g1pp":
         return rows * 3, rows
     if op == "gtpp":
         return rows * fmul[ext[2]], 0
     raise KeyError(op)
+
+
+def quotient_cmp_bits(text):
+    """bits of the reference's quotient_cmp on the twist (ecc/d_param.c:1060-1069, ecc/f_param.c:388-398): the trace
+    recurrence t_(j+1) = t t_j - q t_(j-1) of pbc_mpz_curve_order_extn, divided by r (type d) or r^2 (type f)"""
+    q, r = param_int(text, "q"), param_int(text, "r")
+    typ = [ln.split()[1] for ln in text.splitlines() if ln.startswith("type ")][0]
+    t, k, div = (-(q + 1 - param_int(text, "n")), param_int(text, "k") // 2, r) if typ == "d" else (q - r + 1, 12, r * r)
+    tj, tprev = t, 2
+    for _ in range(k - 1):
+        tj, tprev = t * tj - q * tprev, tj
+    return ((q ** k + 1 - tj) // div).bit_length()
 
 
 def executed_group_macs(workload):
@@ -143,6 +175,8 @@ def cpu_baseline(param_path, op):
     tool = oracle.REF_TOOL
     cores = oracle.usable_cores()      # the cgroup quota, not the logical CPU count of the box
     if not os.path.exists(tool):
+        return None
+    if op in ("gtinvert", "gtdiv", "g2cmp"):      # (ref_tool benchg has no such operation)
         return None
     per = {"g1mul": 400, "g2mul": 200, "gtpow": 2000, "hashg1": 200, "g1pp": 4000, "gtpp": 20000, "blsverify": 150,
            "compress": 400000, "decompress": 4000, "g1add": 100000, "zrinv": 400000, "g1pow2": 300, "gtpow2": 1500}[op]
@@ -319,6 +353,39 @@ def main(args, load_vec, ensure_built, MAC_PEAK):
 
         def gate():
             want = O.pow_multi(group, [IN[sample].cpu().numpy(), IN2[sample].cpu().numpy()], [Z[sample], Z2[sample]])
+            return np.array_equal(OUT[sample].cpu().numpy(), want)
+    elif op in ("gtinvert", "gtdiv"):
+        IN = torch.from_numpy(gt).cuda()[idx].contiguous()
+        IN2 = torch.from_numpy(gt).cuda()[(idx * 3 + 1) % D].contiguous()
+        OUT = torch.empty_like(IN)
+        unit_bytes = (2 if op == "gtinvert" else 3) * LT
+        E = np.tile(np.frombuffer((r - 1).to_bytes(LZ, "big"), np.uint8), (len(sample), 1))
+
+        def step():
+            if op == "gtinvert":
+                P.element_invert_GT_dev(OUT.data_ptr(), IN.data_ptr(), n, s)
+            else:
+                P.element_div_GT_dev(OUT.data_ptr(), IN.data_ptr(), IN2.data_ptr(), n, s)
+
+        def gate():                      # a pairing value's inverse is its (r - 1)-th power
+            if op == "gtinvert":
+                want = O.gt_pow(IN[sample].cpu().numpy(), E)
+            else:
+                want = O.gt_mul(IN[sample].cpu().numpy(), O.gt_pow(IN2[sample].cpu().numpy(), E))
+            return np.array_equal(OUT[sample].cpu().numpy(), want)
+    elif op == "g2cmp":
+        IN = torch.from_numpy(g2).cuda()[idx].contiguous()
+        IN2 = torch.from_numpy(g2).cuda()[(idx * 3 + 1) % D].contiguous()
+        OUT = torch.empty(n, dtype=torch.uint8, device="cuda")
+        unit_bytes = 2 * L2 + 1
+
+        def step():
+            P.element_cmp_dev(2, OUT.data_ptr(), IN.data_ptr(), IN2.data_ptr(), n, s)
+
+        def gate():                      # the complete ladder of the same library on another route, pinned to exact integers in the tests
+            Q = pbc_amd.Pairing(text + "hip_group_slow 1\n")
+            want = Q.element_cmp(2, IN[sample].cpu().numpy(), IN2[sample].cpu().numpy())
+            Q.clear()
             return np.array_equal(OUT[sample].cpu().numpy(), want)
     elif op in ("g1pp", "gtpp"):
         group = 1 if op == "g1pp" else 3

@@ -470,6 +470,51 @@ int pbc_hip_element_mul_mpz_batch_dev(pbc_hip_pairing_t *p, int group, void *d_o
                                       const uint8_t *k /* HOST memory */, size_t klen, size_t n, void *stream);
 size_t pbc_hip_diag_mpz_digits(const uint8_t *k, size_t klen, int w, int8_t *out, size_t cap);
 
+/* Inversion and division on GT: element_invert / element_div (include/pbc_field.h:394, :324) -> mulg_invert / mulg_div
+ * (ecc/pairing.c:203-209).  out[i] = a[i]^-1, resp. a[i] * b[i]^-1 -- the last line of example/bls.c's check
+ * (example/bls.c:104-105), M = C / e(d, U) of identity-based decryption, every ratio of pairings.  Any parameter file of
+ * any type.  Records are read as pbc_hip_element_mul_GT_batch reads them: coordinates reduced mod q on load, ANY field
+ * element, no subgroup assumed; output coordinates are canonical (< q).  The inverse is unique in a field, so the bytes
+ * are the reference's; on elements of order dividing r they are those of pbc_hip_element_mul_mpz_batch(group 3, k = r - 1).
+ * The inverse of 0 and a division by 0 are outside the reference's contract (arith/montfp.c:400 "Requires nonzero a");
+ * here they give the zero record, as pbc_hip_zr_op_batch op 3 does.
+ * The kernels use a^-1 = conj(a) N(a)^-1 with the norm N down to the half-degree subfield (F_q for types a / a1, F_q^d
+ * for types d / g, F_q^6 for type f).  A pairing value has N = 1, its inverse is its conjugate, and a lane that finds
+ * N(a) == 1 runs no inversion at all; any other element takes the subfield inversion in the same kernel
+ * ("hip_group_slow 1": every lane does).  Type e has GT = F_q: every element but 1 is inverted in F_q.  Division is one
+ * fused kernel.  out may be exactly a or exactly b; n == 0 returns 0 and touches nothing.  Errors (non-zero,
+ * pbc_hip_last_error) are found before a device is looked for: null arguments with n > 0.
+ *
+ * element_cmp (include/pbc_field.h:424; the call every example ends with, example/bls.c:105): group 0 (Z_r), 1, 2 or 3.
+ * res[i] = 0 when the reference's element_cmp would return 0 -- EQUAL -- and 1 otherwise; no other value is written.  This
+ * is element_cmp's own convention (`if (!element_cmp(a, b))`), the OPPOSITE of the "1 = yes" bytes of
+ * pbc_hip_is_almost_coddh_batch.  Inputs are not changed; res may not overlap an input.  Records are read as the existing
+ * entry points read them: Z_r as pbc_hip_zr_op_batch, GT as above, points as pbc_hip_element_add_batch (coordinates
+ * reduced mod q; an off-curve record is O; the all-zero record is O -- on types a / a1 that includes (0, 0)).
+ * Groups 0, 3, 1, and group 2 of types a / a1 / e compare the reduced values (fp_cmp arith/montfp.c:450, fq_cmp
+ * arith/fieldquadratic.c:284, polymod_cmp arith/poly.c:814, point_cmp ecc/curve.c:368-373): O equals O and differs
+ * from every finite point.  Group 2 of types d, g and f is a group of COSETS in the reference (ecc/curve.c:29-33;
+ * pbc_hip_element_from_hash_batch multiplies by no cofactor there): curve_cmp (ecc/curve.c:375-391) tests
+ * [quotient_cmp](a - b) == O with quotient_cmp = #E'(F_q^d) / r (ecc/d_param.c:1060-1069, ecc/g_param.c:1336), resp.
+ * #E(F_q^12) / r^2 (ecc/f_param.c:388-398).  So does this call: equal iff [c](a - b) = O on the twist, where c =
+ * gcd(quotient_cmp, order of the twist) -- the same verdict for every point of the twist, since a point's order divides
+ * the twist's; on type f that is the cofactor 2q - r instead of an integer of 1572 to 2559 bits.  Per unit: a - b on the
+ * complete affine law, a ladder over the shared digits of c - 1 as in pbc_hip_element_mul_mpz_batch, and a projective
+ * comparison with -(a - b); a lane that meets an exceptional step is redone on the complete law ("hip_group_slow 1":
+ * every lane).  Errors, found before a device is looked for, in this order: null arguments with n > 0, group outside 0..3.
+ * Host-buffer forms: range split over the device set and staged, as pbc_hip_element_mul_zn_batch.  _dev forms:
+ * device-resident records, enqueued on `stream`, asynchronous.
+ * pbc_hip_diag_quotient_cmp (pure host, no device): for group 2 of types d, g, f the reference's quotient_cmp (which = 0)
+ * or the integer c the kernels walk (which = 1) as a big-endian magnitude, the first `cap` bytes at out; returns its
+ * length, 0 for groups 1 and 3, for the symmetric types and for arguments outside the contract. */
+int pbc_hip_element_invert_GT_batch(pbc_hip_pairing_t *p, uint8_t *out, const uint8_t *a, size_t n);
+int pbc_hip_element_div_GT_batch(pbc_hip_pairing_t *p, uint8_t *out, const uint8_t *a, const uint8_t *b, size_t n);
+int pbc_hip_element_cmp_batch(pbc_hip_pairing_t *p, int group, uint8_t *res, const uint8_t *a, const uint8_t *b, size_t n);
+int pbc_hip_element_invert_GT_batch_dev(pbc_hip_pairing_t *p, void *d_out, const void *d_a, size_t n, void *stream);
+int pbc_hip_element_div_GT_batch_dev(pbc_hip_pairing_t *p, void *d_out, const void *d_a, const void *d_b, size_t n, void *stream);
+int pbc_hip_element_cmp_batch_dev(pbc_hip_pairing_t *p, int group, void *d_res, const void *d_a, const void *d_b, size_t n, void *stream);
+size_t pbc_hip_diag_quotient_cmp(pbc_hip_pairing_t *p, int group, int which, uint8_t *out, size_t cap);
+
 /* Fixed-base powers: replace element_pp_init / element_pp_pow_zn / element_pp_clear (include/pbc_field.h:591-625 ->
  * element_build_base_table / element_pow_base_table, arith/field.c:243-323: a table of in^(w 2^(5 i)), a power = a product
  * of table entries) for a base in G1, G2 (group 1, 2) or GT (group 3) -- the BLS shape: one generator, many secret keys or

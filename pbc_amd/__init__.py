@@ -165,6 +165,14 @@ def lib():
         L.pbc_hip_element_mul_mpz_batch_dev.argtypes = [vp, ci, vp, vp, vp, sz, sz, vp]
         L.pbc_hip_diag_mpz_digits.restype = sz
         L.pbc_hip_diag_mpz_digits.argtypes = [vp, sz, ci, vp, sz]
+        L.pbc_hip_element_invert_GT_batch.argtypes = [vp, vp, vp, sz]
+        L.pbc_hip_element_invert_GT_batch_dev.argtypes = [vp, vp, vp, sz, vp]
+        L.pbc_hip_element_div_GT_batch.argtypes = [vp, vp, vp, vp, sz]
+        L.pbc_hip_element_div_GT_batch_dev.argtypes = [vp, vp, vp, vp, sz, vp]
+        L.pbc_hip_element_cmp_batch.argtypes = [vp, ci, vp, vp, vp, sz]
+        L.pbc_hip_element_cmp_batch_dev.argtypes = [vp, ci, vp, vp, vp, sz, vp]
+        L.pbc_hip_diag_quotient_cmp.restype = sz
+        L.pbc_hip_diag_quotient_cmp.argtypes = [vp, ci, ci, vp, sz]
         _lib = L
     return _lib
 
@@ -208,6 +216,8 @@ EXPORTS = (
     "pbc_hip_element_pp_set_prod_batch", "pbc_hip_element_pp_set_prod_batch_dev", "pbc_hip_diag_element_pp_set_offsets",
     "pbc_hip_element_membership_batch", "pbc_hip_element_membership_batch_dev",
     "pbc_hip_element_mul_mpz_batch", "pbc_hip_element_mul_mpz_batch_dev", "pbc_hip_diag_mpz_digits",
+    "pbc_hip_element_invert_GT_batch", "pbc_hip_element_invert_GT_batch_dev", "pbc_hip_element_div_GT_batch",
+    "pbc_hip_element_div_GT_batch_dev", "pbc_hip_element_cmp_batch", "pbc_hip_element_cmp_batch_dev", "pbc_hip_diag_quotient_cmp",
 )
 
 
@@ -489,6 +499,74 @@ class Pairing:
         out = np.zeros(8 * len(kb) + 1, np.int8)
         n = lib().pbc_hip_diag_mpz_digits(kb, len(kb), w, _np_ptr(out), out.size)
         return out[:n].copy()
+
+    # ---- GT inversion / division, element_cmp (include/pbc_hip.h) ------------------------------------
+    def _gt_records(self, what, recs):
+        import numpy as np
+        recs = np.ascontiguousarray(recs, dtype=np.uint8)
+        lt = self.length_in_bytes_GT
+        n = recs.size // lt
+        if recs.size != n * lt:
+            raise ValueError("%s: %d bytes are no whole number of %d-byte GT records" % (what, recs.size, lt))
+        return recs, n
+
+    def element_invert_GT(self, a):
+        """out[i] = a[i]^-1 for ANY element of the field behind GT (0 gives the zero record)"""
+        import numpy as np
+        a, n = self._gt_records("element_invert_GT", a)
+        out = np.empty((n, self.length_in_bytes_GT), np.uint8)
+        if lib().pbc_hip_element_invert_GT_batch(self._h, _np_ptr(out), _np_ptr(a), n):
+            raise PbcHipError("element_invert_GT: " + _err())
+        return out
+
+    def element_div_GT(self, a, b):
+        """out[i] = a[i] / b[i]"""
+        import numpy as np
+        a, n = self._gt_records("element_div_GT", a)
+        b, nb = self._gt_records("element_div_GT", b)
+        if n != nb:
+            raise ValueError("element_div_GT: %d and %d records" % (n, nb))
+        out = np.empty((n, self.length_in_bytes_GT), np.uint8)
+        if lib().pbc_hip_element_div_GT_batch(self._h, _np_ptr(out), _np_ptr(a), _np_ptr(b), n):
+            raise PbcHipError("element_div_GT: " + _err())
+        return out
+
+    def element_cmp(self, group, a, b):
+        """res[i] = 0 where the reference's element_cmp(a[i], b[i]) returns 0 (EQUAL), 1 otherwise, for records of Z_r, G1,
+        G2 or GT (group 0 / 1 / 2 / 3); on G2 of types d, g, f equal means the same coset.  Returns np.uint8, shape (n,)."""
+        import numpy as np
+        if group not in (0, 1, 2, 3):
+            raise PbcHipError("element_cmp: group must be 0 (Z_r), 1, 2 or 3 (GT)")
+        a = np.ascontiguousarray(a, dtype=np.uint8)
+        b = np.ascontiguousarray(b, dtype=np.uint8)
+        lrec = self._group_len(group)
+        n = a.size // lrec
+        if a.size != n * lrec or b.size != a.size:
+            raise ValueError("element_cmp: both operands must be n records of the group's length")
+        res = np.empty(n, np.uint8)
+        if lib().pbc_hip_element_cmp_batch(self._h, group, _np_ptr(res), _np_ptr(a), _np_ptr(b), n):
+            raise PbcHipError("element_cmp: " + _err())
+        return res
+
+    def element_invert_GT_dev(self, d_out, d_a, n, stream=0):
+        if lib().pbc_hip_element_invert_GT_batch_dev(self._h, d_out, d_a, n, stream):
+            raise PbcHipError("element_invert_GT_dev: " + _err())
+
+    def element_div_GT_dev(self, d_out, d_a, d_b, n, stream=0):
+        if lib().pbc_hip_element_div_GT_batch_dev(self._h, d_out, d_a, d_b, n, stream):
+            raise PbcHipError("element_div_GT_dev: " + _err())
+
+    def element_cmp_dev(self, group, d_res, d_a, d_b, n, stream=0):
+        if lib().pbc_hip_element_cmp_batch_dev(self._h, group, d_res, d_a, d_b, n, stream):
+            raise PbcHipError("element_cmp_dev: " + _err())
+
+    def quotient_cmp(self, group, which=0):
+        """the integer behind element_cmp on G2 of types d, g, f (pbc_hip_diag_quotient_cmp): which = 0 the reference's
+        quotient_cmp, which = 1 the integer the kernels walk; None where element_cmp is a plain comparison"""
+        import numpy as np
+        out = np.zeros(MPZ_MAX_BYTES, np.uint8)
+        n = lib().pbc_hip_diag_quotient_cmp(self._h, group, which, _np_ptr(out), out.size)
+        return int.from_bytes(out[:n].tobytes(), "big") if 0 < n <= out.size else None
 
     # ---- text formats (host side; include/pbc_hip.h) ------------------------------------------
     def _group_len(self, group):

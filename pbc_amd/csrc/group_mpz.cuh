@@ -81,17 +81,19 @@ PBC_DEV void ec_mpz_store(uint8_t *out, const typename F::el &X, const typename 
   F::store(out + F::bytes(), ay);
 }
 
-// The fast lane over a field policy F (group_ops.cuh: FqOps; FdOps / Fq2Ops on the twists), digits of width W.  Returns
-// false -- nothing written -- when the lane needs ec_mpz_complete_lane.
+// The walk of the fast lane over a field policy F (group_ops.cuh: FqOps; FdOps / Fq2Ops on the twists), digits of width W:
+// (X : Y : Z) = [k] (px, py) on the incomplete steps.  Returns true -- `bad` -- when the result cannot be trusted: k = 0,
+// a table that met an exceptional step, Z = 0 at the end.  (The coset compare of group_gtdiv.cuh walks with it too.)
 template <class F, int W>
-PBC_DEV bool ec_mpz_fast_lane(uint8_t *out, const uint8_t *in, const uint32_t *dig, int nd) {
+PBC_DEV bool ec_mpz_fast_walk(typename F::el &X, typename F::el &Y, typename F::el &Z, const typename F::el &px, const typename F::el &py,
+                              const uint32_t *dig, int nd) {
   typedef typename F::el el;
   constexpr int TE = 1 << (W - 2);     // odd multiples 1, 3, ..., 2 TE - 1
   const el one = F::one(), ca = F::curve_a();
   el tab[TE][2];
-  const bool valid = ec_mpz_load<F>(tab[0][0], tab[0][1], in);
+  tab[0][0] = px;
+  tab[0][1] = py;
   bool bad = nd == 0;                  // k = 0: O, left to the complete lane like every other O
-  el X, Y, Z;
   if constexpr (TE > 1) {
     // 2P = (X2 : Y2 : Z2); on the isomorphic curve where 2P is affine the odd multiples follow by mixed additions and go
     // back by Z <- Z Z2; one batched inversion (ec_mul_win_lane)
@@ -150,31 +152,49 @@ PBC_DEV bool ec_mpz_fast_lane(uint8_t *out, const uint8_t *in, const uint32_t *d
       ec_madd_inc<F>(X, Y, Z, tab[idx][0], y2);
     }
   }
-  bad |= F::is0(Z);
+  return bad | F::is0(Z);
+}
+// The fast lane.  Returns false -- nothing written -- when the lane needs ec_mpz_complete_lane.
+template <class F, int W>
+PBC_DEV bool ec_mpz_fast_lane(uint8_t *out, const uint8_t *in, const uint32_t *dig, int nd) {
+  typedef typename F::el el;
+  el x, y, X, Y, Z;
+  const bool valid = ec_mpz_load<F>(x, y, in);
+  const bool bad = ec_mpz_fast_walk<F, W>(X, Y, Z, x, y, dig, nd);
   const bool handled = !valid | !bad;
   if (handled) ec_mpz_store<F>(out, X, Y, Z, !valid);
   return handled;
 }
-// The complete lane: any point of the curve, any k; the same digits read as -1, 0, +1 (mpz_signed_bit), the accumulator
-// from O, every addition with the case analysis of ec_madd_jac (V = O, V = -P, V = P through the double formed beforehand;
-// the double of -P is that of P with Y negated).
+// The walk of the complete lane: (X : Y : Z) = [k] (x, y) for any point of the curve and any k; the same digits read as
+// -1, 0, +1 (mpz_signed_bit), the accumulator from O, every addition with the case analysis of ec_madd_jac (V = O, V = -P,
+// V = P through the double formed beforehand; the double of -P is that of P with Y negated).  Z = 0: the result is O.
 template <class F>
-PBC_DEV void ec_mpz_complete_lane(uint8_t *out, const uint8_t *in, const uint32_t *dig, int nd, int w) {
+PBC_DEV void ec_mpz_complete_walk(typename F::el &X, typename F::el &Y, typename F::el &Z, const typename F::el &x, const typename F::el &y,
+                                  const uint32_t *dig, int nd, int w) {
   typedef typename F::el el;
-  el x, y, ny = F::zero();
-  const bool valid = ec_mpz_load<F>(x, y, in);
+  el ny = F::zero();
   F::sub(ny, ny, y);
   const el one = F::one(), ca = F::curve_a();
   el DX = x, DY = y, DZ = one, nDY = F::zero();
   ec_dbl_jac<F>(DX, DY, DZ, ca);
   F::sub(nDY, nDY, DY);
-  el X = one, Y = one, Z = F::zero();
+  X = one;
+  Y = one;
+  Z = F::zero();
   for (int m = nd ? nd + w - 3 : -1; m >= 0; m--) {
     ec_dbl_jac<F>(X, Y, Z, ca);
     const int d = mpz_signed_bit(dig, nd, w, m);
     if (d > 0) ec_madd_jac<F>(X, Y, Z, x, y, DX, DY, DZ, true);
     else if (d < 0) ec_madd_jac<F>(X, Y, Z, x, ny, DX, nDY, DZ, true);
   }
+}
+// The complete lane
+template <class F>
+PBC_DEV void ec_mpz_complete_lane(uint8_t *out, const uint8_t *in, const uint32_t *dig, int nd, int w) {
+  typedef typename F::el el;
+  el x, y, X, Y, Z;
+  const bool valid = ec_mpz_load<F>(x, y, in);
+  ec_mpz_complete_walk<F>(X, Y, Z, x, y, dig, nd, w);
   ec_mpz_store<F>(out, X, Y, Z, F::is0(Z) | !valid);
 }
 

@@ -236,6 +236,9 @@ struct ProdWs {
   // the workspace's host staging (after get / get2: the table entry is pinned and its issue lock held)
   HostStage *stage() { return own ? own->stage : (pinned ? workspace_stage(P, s) : nullptr); }
 };
+// One call's digit string on its way to the device (pbc_hip_mpz.hip): the workspace's second buffer, one stream-ordered
+// copy from its page-locked staging; `rec` (may be empty): bytes that travel behind the digits (*rec_at).  Null: fail() was called
+const uint32_t *digits_upload(ProdWs &W, const std::vector<int8_t> &dig, const std::vector<uint8_t> &rec, const uint8_t **rec_at, hipStream_t s);
 // The host-buffer path (pbc_hip.hip): chunks over the device set, page-locked buffers in place, anything else staged
 // through per-device chunk buffers that the object keeps.  `launch` enqueues one chunk (device pointers) on a stream.
 typedef std::function<int(void *d_out, const void *d_a, const void *d_b, size_t m, hipStream_t s, const OwnWs *own)> ChunkLaunch;

@@ -110,7 +110,7 @@ static int mpz_recode(int group, const uint8_t *k, size_t klen, std::vector<int8
 // read THEIR digits from the same bytes; the staging is not rewritten before this copy has been made (stage_acquire
 // waits for the event recorded behind the previous one).  The plan of a table set travels the same way.
 // `rec` (may be empty): bytes that travel behind the digits, at the next 16-byte boundary (*rec_at)
-static const uint32_t *digits_upload(ProdWs &W, const std::vector<int8_t> &dig, const std::vector<uint8_t> &rec, const uint8_t **rec_at, hipStream_t s) {
+const uint32_t *digits_upload(ProdWs &W, const std::vector<int8_t> &dig, const std::vector<uint8_t> &rec, const uint8_t **rec_at, hipStream_t s) {
   const size_t off = (dig.size() + 16) & ~(size_t) 15;       // whole words, at least one
   const size_t bytes = off + ((rec.size() + 3) & ~(size_t) 3);
   uint8_t *buf = (uint8_t *) W.get2(bytes);
